@@ -2,8 +2,14 @@
 """Benchmark: LeakDetector training steps on batched L-TOWN-A windows (BASELINE.json
 metric "windowed graphs/sec fwd+bwd on L-TOWN-A at 1/2/4/8 GPU; %HBM roofline").
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
   torchrun --nproc-per-node N ... bench.py --gpus N        (one rank per GPU, RCCL)
+
+A plain run sets up, warms up, times exactly K steps, writes the last timed step's
+outputs when --dump-outputs is given and prints the headline JSON line (value,
+ms_per_step).  Everything else below (per-kernel times, rooflines, PMC traffic, the step
+trace, the exchange's cost, the C4 / C5 / tier / P = 382 / end-to-end legs, the CPU
+baseline) is measured after the timed steps and only with --full.
 
 A step = one full detector training step over one batch of B windows per rank:
 forward (GRU encoder, node init, 2x fused GCN layer, pipe gather, EdgeHead,
@@ -651,6 +657,33 @@ def _conv_ms(predictor, plan, B: int, dev) -> float:
     return _event_ms(run, 20)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath: str, step_loss: torch.Tensor, params: list) -> None:
+    """--dump-outputs DIR: what the last timed step handed to its caller, as DIR/<name>.npy:
+      loss    the step's returned loss (scalar);
+      grads   the gradients the step left in .grad, flat in model.parameters() order;
+      params  the parameters after the step's clip + AdamW update, same order.
+    fp32 as computed (float64 tensors stay float64).  The inputs, the initial weights and
+    the dropout seeds are seeded, so two builds run with the same arguments are comparable
+    array for array."""
+    def host(t: torch.Tensor) -> np.ndarray:
+        t = t.detach()
+        return t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).contiguous().numpy()
+
+    arrays = {"loss": host(step_loss).reshape(1),
+              "grads": np.concatenate([host(p.grad).reshape(-1) for p in params if p.grad is not None]),
+              "params": np.concatenate([host(p).reshape(-1) for p in params])}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    out = Path(dirpath)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+
+
 def _free_port() -> int:
     import socket
     with socket.socket() as so:
@@ -725,8 +758,9 @@ def dry_run(args, rank: int, world: int) -> None:
         full()
     nosync = lambda: None  # noqa: E731
     t_full = _timed_max(full, args.steps, nosync, world)
-    t_nocomm = _timed_max(compute, args.steps, nosync, world)
-    t_ar = _timed_max(lambda: dist.all_reduce(grad), args.steps, nosync, world)
+    if args.full:  # the exchange's cost takes timed passes of its own
+        t_nocomm = _timed_max(compute, args.steps, nosync, world)
+        t_ar = _timed_max(lambda: dist.all_reduce(grad), args.steps, nosync, world)
     if rank == 0:
         out = {"metric": "windowed graphs/sec fwd+bwd on L-TOWN-A", "value": None, "unit": "windows/s",
                "n_gpus": world, "ranks_seen": dist.get_world_size(), "steps": args.steps,
@@ -734,7 +768,8 @@ def dry_run(args, rank: int, world: int) -> None:
                "dry_run": True, "backend": "gloo",
                "config": {"workload": "gradient all-reduce (60,418 fp32) after a fixed CPU matmul stand-in step",
                           "parallelism": f"dp{world}"}}
-        out.update(exchange_fields(t_full, t_nocomm, t_ar, max(args.steps, 1), world, "one bucket, blocking (gloo)"))
+        if args.full:
+            out.update(exchange_fields(t_full, t_nocomm, t_ar, max(args.steps, 1), world, "one bucket, blocking (gloo)"))
         print(json.dumps(out), flush=True)
     dist.destroy_process_group()
 
@@ -745,6 +780,12 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=256, help="windows per rank")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: per-kernel times, "
+                         "rooflines, PMC traffic, the step trace, the exchange's cost, the C4 / C5 / tier / P = 382 / "
+                         "end-to-end legs and the CPU baseline (the --no-* switches below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, gradients and updated parameters as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=24.0, help="seconds of CPU-baseline sampling")
     ap.add_argument("--no-c4", action="store_true", help="skip the configs[3] (C4) leg")
@@ -822,9 +863,6 @@ def main() -> None:
     # fewer steps than the builder's K = 50: VERDICT r05 weak 8.)
     for _ in range(args.warmup):
         step()
-    timer = ops.KernelTimer(["gcn_fwd", "gcn_fwd_l0", "gcn_bwd", "gcn_bwd_l0", "node_init", "gru_fwd", "gru_bwd",
-                             "edge_fwd", "edge_bwd", "pipe_scatter", "pool_head", "pool_head_bwd", "linear_dw"])
-    ops.set_kernel_timer(timer)
 
     def barrier():
         if world > 1:
@@ -843,6 +881,29 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:  # before anything below runs further steps
+        dump_outputs(args.dump_outputs, loss, list(model.parameters()))
+    D = 64
+    head = {
+        "metric": "windowed graphs/sec fwd+bwd on L-TOWN-A", "value": round(B * world * args.steps / elapsed, 2),
+        "unit": "windows/s", "n_gpus": world, "ranks_seen": dist.get_world_size() if world > 1 else 1,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
+        "data": "synthetic residual windows (B,36,29) + time features, random-init weights",
+        "config": {"workload": "L-TOWN-A detector training step (BASELINE configs[2])", "graph": "L-TOWN-A",
+                   "nodes": N, "edge_columns": E1 - N, "pipes": P, "windows_per_rank": B,
+                   "global_batch": B * world, "feat": D, "gnn_layers": 2, "parallelism": f"dp{world}",
+                   "step": "fwd+CE+bwd+allreduce+clip+AdamW, train mode (clip_grad_norm_ + AdamW in one launch, "
+                           "models/optim.py)",
+                   "launch": "eager" if args.eager else "hipgraph (one replay per step, dropout re-drawn on device)"},
+        "final_loss": round(final_loss, 4),
+    }
+    if not args.full:  # the plain run: the headline line and nothing more
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # the exchange's cost: the same captured step with the collectives skipped, and the
     # gradient all-reduce alone (two buckets as the step issues them, or one eagerly)
     if world > 1:
@@ -862,6 +923,9 @@ def main() -> None:
         xchg = exchange_fields(elapsed, elapsed, 0.0, args.steps, 1, "none (one rank)")
     # pass 2: per-kernel HIP-event durations over the same number of steps (eager launches:
     # the events bracket each library call on its stream)
+    timer = ops.KernelTimer(["gcn_fwd", "gcn_fwd_l0", "gcn_bwd", "gcn_bwd_l0", "node_init", "gru_fwd", "gru_bwd",
+                             "edge_fwd", "edge_bwd", "pipe_scatter", "pool_head", "pool_head_bwd", "linear_dw"])
+    ops.set_kernel_timer(timer)
     timer.enabled = True
     for _ in range(args.steps):
         eager_step()
@@ -879,9 +943,6 @@ def main() -> None:
         dist.destroy_process_group()
         return
 
-    ms_per_step = elapsed * 1e3 / args.steps
-    value = B * world * args.steps / elapsed
-    D = 64
     csr_bytes = 4 * (N + 1) + 8 * E1
     fwd_bytes = 8 * B * N * D + csr_bytes           # read x once, write y once
     # layer-L-1 backward: read dy, x and the forward's [y > 0] bits (B*N*D/8 bytes); write dx
@@ -909,17 +970,7 @@ def main() -> None:
                                                                      pipe_ratio=0.5)
     src = "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over the same launch, 2*FETCH+WRITE (gfx950)"
     out = {
-        "metric": "windowed graphs/sec fwd+bwd on L-TOWN-A", "value": round(value, 2), "unit": "windows/s",
-        "n_gpus": world, "ranks_seen": dist.get_world_size() if world > 1 else 1, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
-        "data": "synthetic residual windows (B,36,29) + time features, random-init weights",
-        "config": {"workload": "L-TOWN-A detector training step (BASELINE configs[2])", "graph": "L-TOWN-A",
-                   "nodes": N, "edge_columns": E1 - N, "pipes": P, "windows_per_rank": B,
-                   "global_batch": B * world, "feat": D, "gnn_layers": 2, "parallelism": f"dp{world}",
-                   "step": "fwd+CE+bwd+allreduce+clip+AdamW, train mode (clip_grad_norm_ + AdamW in one launch, "
-                           "models/optim.py)",
-                   "launch": "eager" if args.eager else "hipgraph (one replay per step, dropout re-drawn on device)"},
+        **head,
         "roofline": {"kernel": "lg_gcn_fwd_nm_bits -> k_gcn_fwd_pc, layer 1 (fused gather-aggregate by producer "
                                "waves, fp16x2 MFMA transform + bias/ReLU/dropout by consumer waves, train mode; layer 0 "
                                "reads the compressed node init: kernels_us.gcn_fwd_l0)", "bound": "hbm",
@@ -951,7 +1002,6 @@ def main() -> None:
         "step_gap_us": breakdown["step_gap_us"] if breakdown else None,
         "replay_gap_us": breakdown["replay_gap_us"] if breakdown else None,
         "step_kernels": breakdown,
-        "final_loss": round(final_loss, 4),
     }
     if c4 is not None:
         out["c4"] = c4

@@ -18,7 +18,7 @@ def _json_line(out: str) -> dict:
 def test_bench_gpus2_self_launch_dry_run():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--dry-run"], cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
+                        "--dry-run", "--full"], cwd=REPO, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["dry_run"] is True

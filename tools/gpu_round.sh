@@ -11,11 +11,11 @@ if [[ $WHAT == all || $WHAT == tests ]]; then
   tail -3 "$OUT/tests.log"
 fi
 if [[ $WHAT == all || $WHAT == bench ]]; then
-  timeout -k 10 400 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -30 "$OUT/bench.err"; exit 1; }
+  timeout -k 10 400 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -30 "$OUT/bench.err"; exit 1; }
   cat "$OUT/bench.json"
 fi
 if [[ $WHAT == all || $WHAT == prof ]]; then
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 bench.py --no-cpu-baseline --no-pmc --steps 20 --warmup 5 > "$OUT/bench_prof.json" 2> "$OUT/prof.err" || { echo "prof failed"; tail -20 "$OUT/prof.err"; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-pmc --steps 20 --warmup 5 > "$OUT/bench_prof.json" 2> "$OUT/prof.err" || { echo "prof failed"; tail -20 "$OUT/prof.err"; exit 1; }
   find "$OUT/prof" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats.csv" \;
   head -25 "$OUT/kernel_stats.csv" | cut -c1-200
 fi
