@@ -224,6 +224,69 @@ int lg_graph_build(const int64_t* edge_index, int64_t E, int64_t N,
                    int32_t* rowptr_t, int32_t* col_t, float* w_t,
                    void* workspace, int64_t ws_bytes, lg_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * Edge weights (PyG GCNConv.forward(x, edge_index, edge_weight): gcn_norm with weights).
+ * Added to ABI 26 WITHOUT a version bump: additions only, no existing symbol or signature
+ * changed, so a caller built against the earlier 26 keeps working.
+ * Semantics (PyG 2.x gcn_norm with edge_weight):
+ *   add_self_loops: add_remaining_self_loops: edges with src == dst leave the edge list, one
+ *                   loop per node is appended; its weight is fill_value, or, when the input
+ *                   held a self-loop edge on that node, that edge's weight (the LAST such
+ *                   edge in edge order); earlier self-loop edges of the node are dropped.
+ *                   Without add_self_loops nothing is removed or appended.
+ *   degree:         deg[d] = weights into d summed in ascending edge order, the appended
+ *                   loop last (the order of a CPU index_add_); summed per row after the
+ *                   per-row sort, no float atomics, so runs are bit-identical.
+ *   normalize:      dis = deg^-1/2 (inf -> 0; each step in fp64, rounded once);
+ *                   w = (dis[src] * weight) * dis[dst] in fp32.  normalize = 0: w = weight.
+ *   Weights are expected to be non-negative and are not checked: a negative degree gives
+ *   NaN, as in PyG.
+ * Slot-to-edge map: eid / eid_t (int32, one per CSR slot of the forward / transposed CSR)
+ * hold the input edge the slot came from; an appended loop slot holds the self-loop edge
+ * that supplied its weight, or -1 when the loop took fill_value.  Every input edge owns at
+ * most one slot of each CSR (dropped self loops own none).
+ *
+ * lg_graph_build_w: lg_graph_build with a device edge_weight (fp32 [E]; may be NULL when
+ *   E == 0).  Also writes eid, eid_t (int32 [E+N]) and dis (fp32 [N], kept for the backward).
+ * lg_graph_reweight: the structure of an earlier lg_graph_build_w plus a NEW edge_weight:
+ *   recomputes dis, w and w_t only (learned weights change every step, edge_index does not).
+ *   Kernel launches on `stream` only: no allocation, no host sync, capturable.
+ * lg_gcn_norm_bwd: G[k] = dL/dw[k] in forward-CSR order -> dedge_weight = dL/d edge_weight
+ *   (fp32 [E]), deterministic, no float atomics: G is routed to the edges through eid (plain
+ *   stores), then per node ddis[n] = sum over row n of G v dis[src] + sum over transposed row
+ *   n of G v dis[dst] (a loop is in both: its coefficient is v dis[n]^2), ddeg = -1/2 dis^3
+ *   ddis, and dv[e] = dis[s] dis[d] G_e + ddeg[d]; the self-loop edge that supplied a loop
+ *   weight gets dis[n]^2 G_loop + ddeg[n], dropped edges 0, fill loops nothing.
+ *   normalize = 0: dv[e] = G_e.  workspace: lg_gcn_norm_bwd_workspace_bytes (E floats).
+ * ------------------------------------------------------------------------- */
+int64_t lg_graph_build_w_workspace_bytes(int64_t E, int64_t N);
+int lg_graph_build_w(const int64_t* edge_index, const float* edge_weight, int64_t E, int64_t N,
+                     int add_self_loops, int normalize, float fill_value,
+                     int32_t* rowptr, int32_t* col, float* w, int32_t* eid,
+                     int32_t* rowptr_t, int32_t* col_t, float* w_t, int32_t* eid_t, float* dis,
+                     void* workspace, int64_t ws_bytes, lg_stream_t stream);
+int lg_graph_reweight(const int32_t* rowptr, const int32_t* col, const int32_t* eid,
+                      const int32_t* rowptr_t, const int32_t* col_t, const int32_t* eid_t,
+                      const float* edge_weight, int64_t E, int64_t N, int normalize, float fill_value,
+                      float* dis, float* w, float* w_t, lg_stream_t stream);
+int64_t lg_gcn_norm_bwd_workspace_bytes(int64_t E, int64_t N);
+int lg_gcn_norm_bwd(const float* G, const int32_t* rowptr, const int32_t* col, const int32_t* eid,
+                    const int32_t* rowptr_t, const int32_t* col_t, const int32_t* eid_t,
+                    const float* dis, const float* edge_weight, int64_t E, int64_t N, int normalize,
+                    float fill_value, float* dedge_weight, void* workspace, int64_t ws_bytes,
+                    lg_stream_t stream);
+
+/* Sampled dense-dense product over a CSR: out[k] = sum_c a[row(k)][c] * b[col[k]][c] for
+ * every slot k < rowptr[N] (row(k) = the row whose range holds k); elements of out past
+ * rowptr[N] stay untouched.  Any C; row strides lda, ldb >= C (floats).  The gradient of a
+ * propagate with respect to its coefficients: dL/dw[k] = dy[row k] . x[col k].  One wave
+ * walks a row with its a row in registers, the lanes across columns (16-byte loads when C,
+ * both strides and both bases allow), several neighbour rows in flight, and a fixed-shape
+ * wave reduction: deterministic, no atomics.  32-bit offsets when N * ld fits, else 64-bit.
+ * N == 0 or C == 0 returns LG_OK without a launch.  (Added to ABI 26 without a bump.) */
+int lg_sddmm_cols(const int32_t* rowptr, const int32_t* col, const float* a, int64_t lda,
+                  const float* b, int64_t ldb, float* out, int64_t N, int64_t C, lg_stream_t stream);
+
 /* Node table of the node-major kernels, once per graph (and once for the transposed CSR):
  * one 64-byte record per node = {e0, e1, (col, float_as_int(w)) x 6, self, node} so a tile
  * reads its CSR row with ONE scalar load.  self = position (< 6) of the row's entry whose

@@ -2297,7 +2297,9 @@ __device__ __forceinline__ void rows_gather(const RowsRec& r, const int2* __rest
                 f32x4, __builtin_amdgcn_raw_buffer_load_b128(src, lo + static_cast<uint32_t>(pa.x) * (4u * D), 0, 0));
             pk_fma4(acc[k], __int_as_float(pa.y), t);
         }
-        if (OWN && (r.self[k] < 0) && r.e0[k] < r.e1[k])  // self entry past the inline six
+        // self entry past the inline six, or none at all (add_self_loops = 0: an EMPTY row still owns
+        // its dz row, which db sums); a slot past N has an all-zero record, self = 0, and never loads
+        if (OWN && (r.self[k] < 0))
             own[k] = __builtin_bit_cast(
                 f32x4, __builtin_amdgcn_raw_buffer_load_b128(src, lo + static_cast<uint32_t>(r.node[k]) * (4u * D), 0, 0));
     }

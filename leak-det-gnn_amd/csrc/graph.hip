@@ -5,6 +5,11 @@
 // atomics, then a per-row insertion sort that restores ascending edge order so the
 // CSR is bit-identical from run to run and visits each row's entries in the order
 // PyG's scatter_add does (edges ascending, appended self loop last).
+//
+// Edge weights (lg_graph_build_w / lg_graph_reweight / lg_gcn_norm_bwd): the same structure
+// build with the sorted edge ids kept as the slot-to-edge map, then the weighted degree summed
+// per row in slot order (no float atomics) and the backward of that normalisation.  The
+// reweight and its backward run every step when the weights are learned.
 #include <algorithm>
 #include <utility>
 #include <vector>
@@ -120,6 +125,114 @@ __global__ void k_finalize(const int64_t* __restrict__ ei, int64_t E, int64_t N,
     if (add_loops) {
         col_t[bt + ct] = static_cast<int32_t>(n);
         w_t[bt + ct] = normalize ? (dn * fill) * dn : fill;
+    }
+}
+
+// ------------------------------------------------------------------ edge weights
+// loop_e[n] = the LAST input edge (n, n) in edge order, -1 if none (integer max: order-free).
+__global__ void k_loop_edge(const int64_t* __restrict__ ei, int64_t E, int64_t N, int32_t* __restrict__ loop_e) {
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const int64_t s = ei[e], d = ei[E + e];
+    if (s != d || s < 0 || s >= N) return;
+    atomicMax(&loop_e[s], static_cast<int32_t>(e));
+}
+
+// Per row: restore ascending edge order of the slot-to-edge map (filled by k_fill_edges), then
+// write col and the loop slot (col = n, eid = the self-loop edge that supplies its weight or -1).
+__global__ void k_structure_w(const int64_t* __restrict__ ei, int64_t E, int64_t N, int add_loops,
+                              const int32_t* __restrict__ cnt, const int32_t* __restrict__ cnt_t,
+                              const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rowptr_t,
+                              const int32_t* __restrict__ loop_e, int32_t* __restrict__ col,
+                              int32_t* __restrict__ eid, int32_t* __restrict__ col_t, int32_t* __restrict__ eid_t) {
+    const int64_t n = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const int32_t b = rowptr[n], c = cnt[n], bt = rowptr_t[n], ct = cnt_t[n];
+    insertion_sort(eid + b, c);
+    insertion_sort(eid_t + bt, ct);
+    for (int i = 0; i < c; ++i) col[b + i] = static_cast<int32_t>(ei[eid[b + i]]);
+    for (int i = 0; i < ct; ++i) col_t[bt + i] = static_cast<int32_t>(ei[E + eid_t[bt + i]]);
+    if (add_loops) {
+        col[b + c] = col_t[bt + ct] = static_cast<int32_t>(n);
+        eid[b + c] = eid_t[bt + ct] = loop_e[n];
+    }
+}
+
+// weight of a CSR slot: its edge's, or fill for an appended loop no edge supplied
+__device__ __forceinline__ float slot_weight(int32_t e, const float* __restrict__ ew, int64_t E, float fill) {
+    return (e >= 0 && e < E) ? ew[e] : fill;
+}
+
+// phase 0: deg[n] = the row's weights summed in slot order (edges ascending, loop last), dis =
+// deg^-1/2 by k_finalize's fp64-then-round-once steps.  phase 1 (all dis[] final): w, w_t.
+__global__ void k_reweight(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                           const int32_t* __restrict__ eid, const int32_t* __restrict__ rowptr_t,
+                           const int32_t* __restrict__ col_t, const int32_t* __restrict__ eid_t,
+                           const float* __restrict__ ew, int64_t E, int64_t N, int normalize, float fill,
+                           float* __restrict__ dis, float* __restrict__ w, float* __restrict__ w_t, int phase) {
+    const int64_t n = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const int32_t b = rowptr[n], e1 = rowptr[n + 1];
+    if (phase == 0) {
+        float deg = 0.0f;
+        for (int k = b; k < e1; ++k) deg += slot_weight(eid[k], ew, E, fill);
+        const float sq = static_cast<float>(sqrt(static_cast<double>(deg)));
+        const float r = static_cast<float>(1.0 / static_cast<double>(sq));
+        dis[n] = (deg == 0.0f || r == __builtin_huge_valf()) ? 0.0f : r;  // inf -> 0; deg < 0 -> NaN, as PyG
+        return;
+    }
+    const float dn = dis[n];
+    for (int k = b; k < e1; ++k) {
+        const float v = slot_weight(eid[k], ew, E, fill);
+        const int32_t s = col[k];
+        w[k] = normalize ? (dis[(s >= 0 && s < N) ? s : n] * v) * dn : v;
+    }
+    const int32_t bt = rowptr_t[n], et = rowptr_t[n + 1];
+    for (int k = bt; k < et; ++k) {
+        const float v = slot_weight(eid_t[k], ew, E, fill);
+        const int32_t d = col_t[k];
+        w_t[k] = normalize ? (dn * v) * dis[(d >= 0 && d < N) ? d : n] : v;
+    }
+}
+
+// G[k] -> Ge[eid[k]]: every edge owns at most one forward slot, so these are plain stores.
+__global__ void k_route_edges(const float* __restrict__ G, const int32_t* __restrict__ rowptr,
+                              const int32_t* __restrict__ eid, int64_t E, int64_t N, int64_t cap,
+                              float* __restrict__ Ge) {
+    const int64_t k = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (k >= cap || k >= rowptr[N]) return;
+    const int32_t e = eid[k];
+    if (e >= 0 && e < E) Ge[e] = G[k];
+}
+
+// Per node: ddis from the row and the transposed row (fixed slot order), ddeg, then dv of the
+// row's edges (the loop slot's supplying edge has col == n, so one formula covers it).
+__global__ void k_norm_bwd(const float* __restrict__ G, const float* __restrict__ Ge,
+                           const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                           const int32_t* __restrict__ eid, const int32_t* __restrict__ rowptr_t,
+                           const int32_t* __restrict__ col_t, const int32_t* __restrict__ eid_t,
+                           const float* __restrict__ dis, const float* __restrict__ ew, int64_t E, int64_t N,
+                           float fill, float* __restrict__ dv) {
+    const int64_t n = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const int32_t b = rowptr[n], e1 = rowptr[n + 1];
+    const float dn = dis[n];
+    float ddis = 0.0f;
+    for (int k = b; k < e1; ++k) {
+        const int32_t s = col[k];
+        ddis += (G[k] * slot_weight(eid[k], ew, E, fill)) * dis[(s >= 0 && s < N) ? s : n];
+    }
+    const int32_t bt = rowptr_t[n], et = rowptr_t[n + 1];
+    for (int k = bt; k < et; ++k) {
+        const int32_t e = eid_t[k], d = col_t[k];
+        // a fill loop (no edge): its G is the forward row's last slot (the appended loop)
+        const float g = (e >= 0 && e < E) ? Ge[e] : (e1 > b ? G[e1 - 1] : 0.0f);
+        ddis += (g * slot_weight(e, ew, E, fill)) * dis[(d >= 0 && d < N) ? d : n];
+    }
+    const float ddeg = dn != 0.0f ? -0.5f * dn * dn * dn * ddis : 0.0f;
+    for (int k = b; k < e1; ++k) {
+        const int32_t e = eid[k], s = col[k];
+        if (e >= 0 && e < E) dv[e] = (dis[(s >= 0 && s < N) ? s : n] * dn) * G[k] + ddeg;
     }
 }
 
@@ -267,6 +380,98 @@ extern "C" int lg_graph_build(const int64_t* edge_index, int64_t E, int64_t N, i
                                                    phase);
         LG_RET_IF_LAUNCH_FAILED();
     }
+    return LG_OK;
+}
+
+extern "C" int64_t lg_graph_build_w_workspace_bytes(int64_t E, int64_t N) {
+    if (E < 0 || N < 0) return LG_EINVAL;
+    // cnt, cnt_t, cur, cur_t, loop_e : N each (the slot-to-edge maps are filled in place)
+    return align256(4 * (5 * N) + 64);
+}
+
+extern "C" int lg_graph_reweight(const int32_t* rowptr, const int32_t* col, const int32_t* eid,
+                                 const int32_t* rowptr_t, const int32_t* col_t, const int32_t* eid_t,
+                                 const float* edge_weight, int64_t E, int64_t N, int normalize, float fill_value,
+                                 float* dis, float* w, float* w_t, lg_stream_t stream) {
+    if (E < 0 || N <= 0 || N > INT32_MAX / 2 || E > INT32_MAX / 2) return LG_EINVAL;
+    if (!rowptr || !col || !eid || !rowptr_t || !col_t || !eid_t || (E > 0 && !edge_weight) || !dis || !w || !w_t)
+        return LG_EINVAL;
+    hipStream_t s = lg_stream(stream);
+    for (int phase = 0; phase < 2; ++phase) {
+        k_reweight<<<nblocks(N), kThreads, 0, s>>>(rowptr, col, eid, rowptr_t, col_t, eid_t, edge_weight, E, N,
+                                                   normalize ? 1 : 0, fill_value, dis, w, w_t, phase);
+        LG_RET_IF_LAUNCH_FAILED();
+    }
+    return LG_OK;
+}
+
+extern "C" int lg_graph_build_w(const int64_t* edge_index, const float* edge_weight, int64_t E, int64_t N,
+                                int add_self_loops, int normalize, float fill_value, int32_t* rowptr, int32_t* col,
+                                float* w, int32_t* eid, int32_t* rowptr_t, int32_t* col_t, float* w_t,
+                                int32_t* eid_t, float* dis, void* workspace, int64_t ws_bytes,
+                                lg_stream_t stream) {
+    if (E < 0 || N <= 0 || N > INT32_MAX / 2 || E > INT32_MAX / 2) return LG_EINVAL;
+    if ((E > 0 && (!edge_index || !edge_weight)) || !rowptr || !col || !w || !eid || !rowptr_t || !col_t || !w_t ||
+        !eid_t || !dis || !workspace)
+        return LG_EINVAL;
+    if (ws_bytes < lg_graph_build_w_workspace_bytes(E, N)) return LG_EINVAL;
+    hipStream_t s = lg_stream(stream);
+    int32_t* cnt = static_cast<int32_t*>(workspace);
+    int32_t* cnt_t = cnt + N;
+    int32_t* cur = cnt_t + N;
+    int32_t* cur_t = cur + N;
+    int32_t* loop_e = cur_t + N;
+    if (hipMemsetAsync(cnt, 0, sizeof(int32_t) * 4 * N, s) != hipSuccess) return LG_EHIP;
+    if (hipMemsetAsync(loop_e, 0xFF, sizeof(int32_t) * N, s) != hipSuccess) return LG_EHIP;  // -1
+    const int drop = add_self_loops ? 1 : 0;
+    if (E > 0) {
+        k_count_edges<<<nblocks(E), kThreads, 0, s>>>(edge_index, E, N, drop, cnt, cnt_t);
+        if (drop) k_loop_edge<<<nblocks(E), kThreads, 0, s>>>(edge_index, E, N, loop_e);
+        LG_RET_IF_LAUNCH_FAILED();
+    }
+    k_scan_rows<<<1, 1024, 0, s>>>(cnt, N, drop, rowptr);
+    k_scan_rows<<<1, 1024, 0, s>>>(cnt_t, N, drop, rowptr_t);
+    LG_RET_IF_LAUNCH_FAILED();
+    if (E > 0) {
+        k_fill_edges<<<nblocks(E), kThreads, 0, s>>>(edge_index, E, N, drop, rowptr, rowptr_t, cur, cur_t, eid, eid_t);
+        LG_RET_IF_LAUNCH_FAILED();
+    }
+    k_structure_w<<<nblocks(N), kThreads, 0, s>>>(edge_index, E, N, drop, cnt, cnt_t, rowptr, rowptr_t, loop_e, col, eid,
+                                                  col_t, eid_t);
+    LG_RET_IF_LAUNCH_FAILED();
+    return lg_graph_reweight(rowptr, col, eid, rowptr_t, col_t, eid_t, edge_weight, E, N, normalize, fill_value, dis, w,
+                             w_t, stream);
+}
+
+extern "C" int64_t lg_gcn_norm_bwd_workspace_bytes(int64_t E, int64_t N) {
+    if (E < 0 || N < 0) return LG_EINVAL;
+    return align256(4 * E + 64);  // G routed to the edges
+}
+
+extern "C" int lg_gcn_norm_bwd(const float* G, const int32_t* rowptr, const int32_t* col, const int32_t* eid,
+                               const int32_t* rowptr_t, const int32_t* col_t, const int32_t* eid_t, const float* dis,
+                               const float* edge_weight, int64_t E, int64_t N, int normalize, float fill_value,
+                               float* dedge_weight, void* workspace, int64_t ws_bytes, lg_stream_t stream) {
+    if (E < 0 || N <= 0 || N > INT32_MAX / 2 || E > INT32_MAX / 2) return LG_EINVAL;
+    if (!G || !rowptr || !col || !eid || !rowptr_t || !col_t || !eid_t || !dis || !workspace ||
+        (E > 0 && (!edge_weight || !dedge_weight)))
+        return LG_EINVAL;
+    if (ws_bytes < lg_gcn_norm_bwd_workspace_bytes(E, N)) return LG_EINVAL;
+    if (E == 0) return LG_OK;
+    hipStream_t s = lg_stream(stream);
+    // dropped edges (earlier duplicate self loops) own no slot: their gradient is 0
+    if (hipMemsetAsync(dedge_weight, 0, sizeof(float) * E, s) != hipSuccess) return LG_EHIP;
+    const int64_t cap = E + N;
+    if (!normalize) {  // w = weight: dv[e] = G_e
+        k_route_edges<<<nblocks(cap), kThreads, 0, s>>>(G, rowptr, eid, E, N, cap, dedge_weight);
+        LG_RET_IF_LAUNCH_FAILED();
+        return LG_OK;
+    }
+    float* Ge = static_cast<float*>(workspace);
+    k_route_edges<<<nblocks(cap), kThreads, 0, s>>>(G, rowptr, eid, E, N, cap, Ge);
+    k_norm_bwd<<<nblocks(N), kThreads, 0, s>>>(G, Ge, rowptr, col, eid, rowptr_t, col_t, eid_t, dis, edge_weight, E, N,
+                                               fill_value, dedge_weight);
+    LG_RET_IF_LAUNCH_FAILED();
     return LG_OK;
 }
 

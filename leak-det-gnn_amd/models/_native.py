@@ -55,6 +55,13 @@ SIGNATURES = {
     "lg_timing_elapsed": (_i32, [_i32, _p]),
     "lg_graph_workspace_bytes": (_i64, [_i64, _i64]),
     "lg_graph_build": (_i32, [_p, _i64, _i64, _i32, _i32, _f32, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    # edge weights (added to ABI 26 without a bump: additions only)
+    "lg_graph_build_w_workspace_bytes": (_i64, [_i64, _i64]),
+    "lg_graph_build_w": (_i32, [_p, _p, _i64, _i64, _i32, _i32, _f32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "lg_graph_reweight": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _f32, _p, _p, _p, _p]),
+    "lg_gcn_norm_bwd_workspace_bytes": (_i64, [_i64, _i64]),
+    "lg_gcn_norm_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _f32, _p, _p, _i64, _p]),
+    "lg_sddmm_cols": (_i32, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _p]),
     "lg_nm_table_build": (_i32, [_p, _p, _i64, _p, _p, _p]),
     "lg_rcm_order": (_i32, [_p, _i64, _i64, _p]),
     "lg_incidence_workspace_bytes": (_i64, [_i64, _i64]),

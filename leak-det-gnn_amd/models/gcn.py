@@ -8,7 +8,7 @@ reference; the semantics restated here are PyG 2.x's published ones:
           normalize=True, bias=True)
      lin = Linear(in, out, bias=False, glorot init)  -> state key ``lin.weight`` [out, in]
      bias = zeros(out)                                -> state key ``bias``
-     forward(x, edge_index) = propagate(gcn_norm(edge_index), lin(x)) + bias
+     forward(x, edge_index, edge_weight=None) = propagate(gcn_norm(edge_index, edge_weight), lin(x)) + bias
   global_mean_pool(x, batch, size=None) = scatter(x, batch, reduce='mean', dim_size=size)
 
 Here forward runs the registered op leakgnn::gcn_conv (models/library.py: one fused HIP
@@ -24,6 +24,18 @@ hit with no device work (so a HIP-graph-captured step never syncs); any other te
 is compared element-wise with a private copy.  Keying on the storage address alone
 would reuse a stale CSR when the caching allocator hands a freed edge_index's
 address to a different graph of the same shape.
+
+edge_weight (a floating tensor of shape (E,), PyG's third argument): the weighted gcn_norm is
+built on the device (lg_graph_build_w: add_remaining_self_loops with the carried-over weight of
+an input self loop, the degree summed per row in edge order, deterministic) and honours
+improved / add_self_loops / normalize on both paths.  The structure stays cached per edge_index;
+a weight tensor other than the last one, or the same one modified in place, only re-runs the
+normalisation (GCNGraph.reweight: lg_graph_reweight and the node tables, no host sync).
+Weights that require grad get their gradient: gcn_conv / spmm_cols return dL/dw by an SDDMM
+(lg_sddmm_cols), and leakgnn::gcn_edge_norm's formula (lg_gcn_norm_bwd) carries it through the
+normalisation to the edges, without float atomics.  Weights are expected to be non-negative and
+are not checked: a negative degree gives NaN, as in PyG.  With edge_weight=None nothing changes
+(including the unweighted builder's treatment of input self loops, which take the fill value).
 """
 from __future__ import annotations
 
@@ -35,7 +47,7 @@ import torch
 import torch.nn as nn
 
 from . import library  # noqa: F401  (registers the leakgnn:: ops)
-from .ops import SUPPORTED_D, GCNGraph, _f32
+from .ops import SUPPORTED_D, GCNGraph, _f32, check_edge_weight
 
 
 def _glorot_(t: torch.Tensor) -> None:
@@ -74,6 +86,14 @@ class GCNConv(nn.Module):
         self._graph = None
         self._graph_ref = None
         self._graph_ver = -1
+        # the weighted graph (forward(..., edge_weight)): its own structure cache and the weights' key
+        self._wgraph: Optional[GCNGraph] = None
+        self._wgraph_key = None
+        self._wgraph_ei: Optional[torch.Tensor] = None
+        self._wgraph_ref = None
+        self._wgraph_ver = -1
+        self._wgraph_wref = None
+        self._wgraph_wver = -1
 
     def graph_for(self, edge_index: torch.Tensor, num_nodes: int, device: torch.device) -> GCNGraph:
         """The cached CSR of `edge_index`.  Fast path (no device sync, capture-safe): the SAME
@@ -99,10 +119,52 @@ class GCNConv(nn.Module):
         self._graph_ver = edge_index._version
         return self._graph
 
+    def weighted_graph_for(self, edge_index: torch.Tensor, edge_weight: torch.Tensor, num_nodes: int,
+                           device: torch.device) -> GCNGraph:
+        """The cached weighted CSR.  The structure is keyed on edge_index exactly as graph_for
+        keys the unweighted one (its own cache: a weighted graph also carries the slot-to-edge
+        map).  The weights: the same tensor object at the same version counter is a hit with no
+        device work; any other weight tensor (a fresh one, or one modified in place: its version
+        counter moved) is a GCNGraph.reweight: device work only, no host sync, no rebuild.
+        Weights that require grad are re-attached on every call, since each forward needs its
+        own autograd edge to them."""
+        key = (tuple(edge_index.shape), edge_index.dtype, int(num_nodes), device)
+        ref = self._wgraph_ref() if self._wgraph_ref is not None else None
+        same_ei = (self._wgraph is not None and self._wgraph_key == key and ref is edge_index
+                   and edge_index._version == self._wgraph_ver)
+        if not same_ei:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("GCNConv: a new edge_index inside HIP graph capture; run one eager forward with "
+                                   "it first (the CSR is built and cached outside the capture)")
+            ei = edge_index.to(device)
+            if (self._wgraph is None or self._wgraph_key != key or self._wgraph_ei is None
+                    or not torch.equal(self._wgraph_ei, ei)):
+                self._wgraph = GCNGraph.build(edge_index, num_nodes, device, add_self_loops=self.add_self_loops,
+                                              normalize=self.normalize, improved=self.improved,
+                                              edge_weight=edge_weight)
+                self._wgraph_key = key
+                self._wgraph_ei = ei.clone()
+                # the build took these values (not the autograd edge: tracked weights reweight below)
+                self._wgraph_wref = weakref.ref(edge_weight)
+                self._wgraph_wver = edge_weight._version
+            self._wgraph_ref = weakref.ref(edge_index)
+            self._wgraph_ver = edge_index._version
+        wref = self._wgraph_wref() if self._wgraph_wref is not None else None
+        tracked = edge_weight.requires_grad and torch.is_grad_enabled()
+        if tracked or wref is not edge_weight or edge_weight._version != self._wgraph_wver:
+            self._wgraph.reweight(edge_weight)
+            self._wgraph_wref = weakref.ref(edge_weight)
+            self._wgraph_wver = edge_weight._version
+        return self._wgraph
+
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_weight: Optional[torch.Tensor] = None):
         if edge_weight is not None:
-            raise NotImplementedError("edge_weight is not used on the Leak-det-gnn path")
-        g = self.graph_for(edge_index, x.size(0), x.device)
+            if edge_index.dim() != 2 or edge_index.size(0) != 2:
+                raise ValueError(f"edge_index must be (2, E), got {tuple(edge_index.shape)}")
+            check_edge_weight(edge_weight, edge_index.size(1))
+            g = self.weighted_graph_for(edge_index, edge_weight, x.size(0), x.device)
+        else:
+            g = self.graph_for(edge_index, x.size(0), x.device)
         if self.in_channels == self.out_channels and self.in_channels in SUPPORTED_D:
             return torch.ops.leakgnn.gcn_conv(_f32(x), _f32(self.lin.weight), _f32(self.bias), g.rowptr, g.col, g.w,
                                               g.rowptr_t, g.col_t, g.w_t, g.nodetab, g.pairs, g.nodetab_t, g.pairs_t)

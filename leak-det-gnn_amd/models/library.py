@@ -6,6 +6,9 @@ Python, so torch.compile / torch.export / any dispatcher-level caller sees them 
 ordinary ops (fake / meta implementations give output shapes without running kernels).
 
   leakgnn::gcn_conv            PyG GCNConv.forward (detector.py:163,199): Ahat (x W^T) + b
+  leakgnn::spmm_cols           the propagate of GCNConv's general path (any width)
+  leakgnn::gcn_edge_norm       PyG gcn_norm with edge_weight over a built structure (w, w_t, dis)
+  leakgnn::sddmm_cols          dL/dw of a propagate (no autograd of its own)
   leakgnn::mean_pool           PyG global_mean_pool over B equal windows (detector.py:215)
   leakgnn::sensor_proj         sensor_to_node on the sensor rows (detector.py:184-189)
   leakgnn::gru_encoder         SharedSensorGRUEncoder's GRU (detector.py:60-73)
@@ -135,15 +138,22 @@ def _(dy, x, weight, rowptr_t, col_t, w_t, nodetab_t, pairs_t):
 
 
 def _gcn_conv_setup(ctx, inputs, output):
-    x, weight, bias, _, _, _, rowptr_t, col_t, w_t, _, _, nodetab_t, pairs_t = inputs
+    x, weight, bias, rowptr, col, _, rowptr_t, col_t, w_t, _, _, nodetab_t, pairs_t = inputs
     ctx.has_bias = bias is not None
-    ctx.save_for_backward(x, weight, rowptr_t, col_t, w_t, nodetab_t, pairs_t)
+    ctx.w_grad = bool(ctx.needs_input_grad[5])  # w: learned edge weights (leakgnn::gcn_edge_norm)
+    ctx.save_for_backward(x, weight, rowptr_t, col_t, w_t, nodetab_t, pairs_t, *((rowptr, col) if ctx.w_grad else ()))
 
 
 def _gcn_conv_bwd(ctx, dy):
-    x, weight, rowptr_t, col_t, w_t, nodetab_t, pairs_t = ctx.saved_tensors
+    x, weight, rowptr_t, col_t, w_t, nodetab_t, pairs_t = ctx.saved_tensors[:7]
     dx, dW, db = torch.ops.leakgnn.gcn_conv_backward(dy, x, weight, rowptr_t, col_t, w_t, nodetab_t, pairs_t)
-    return (dx, dW, (db if ctx.has_bias else None)) + (None,) * 10
+    dw = None
+    if ctx.w_grad:  # dL/dw[k] = dy[n] . (x W^T)[col k]: one library GEMM, then the SDDMM over the CSR
+        rowptr, col = ctx.saved_tensors[7:]
+        with torch.autocast("cuda", enabled=False):
+            z = x @ weight.t()
+        dw = torch.ops.leakgnn.sddmm_cols(rowptr, col, dy, z)
+    return (dx, dW, (db if ctx.has_bias else None), None, None, dw) + (None,) * 7
 
 
 gcn_conv.register_autograd(_gcn_conv_bwd, setup_context=_gcn_conv_setup)
@@ -174,19 +184,118 @@ def _(x, bias, rowptr, col, w, rowptr_t, col_t, w_t):
 
 
 def _spmm_cols_setup(ctx, inputs, output):
-    _, bias, _, _, _, rowptr_t, col_t, w_t = inputs
+    x, bias, rowptr, col, _, rowptr_t, col_t, w_t = inputs
     ctx.has_bias = bias is not None
-    ctx.save_for_backward(rowptr_t, col_t, w_t)
+    ctx.w_grad = bool(ctx.needs_input_grad[4])  # w: learned edge weights (leakgnn::gcn_edge_norm)
+    ctx.save_for_backward(rowptr_t, col_t, w_t, *((x, rowptr, col) if ctx.w_grad else ()))
 
 
 def _spmm_cols_bwd(ctx, dy):
-    rowptr_t, col_t, w_t = ctx.saved_tensors
+    rowptr_t, col_t, w_t = ctx.saved_tensors[:3]
     # dx = Ahat^T dy: the same propagate over the transposed CSR (its rows are the columns of Ahat)
     dx = torch.ops.leakgnn.spmm_cols(dy, None, rowptr_t, col_t, w_t, rowptr_t, col_t, w_t)
-    return dx, (dy.sum(0) if ctx.has_bias else None), None, None, None, None, None, None
+    dw = None
+    if ctx.w_grad:  # dL/dw[k] = dy[n] . x[col k]
+        x, rowptr, col = ctx.saved_tensors[3:]
+        dw = torch.ops.leakgnn.sddmm_cols(rowptr, col, dy, x)
+    return dx, (dy.sum(0) if ctx.has_bias else None), None, None, dw, None, None, None
 
 
 spmm_cols.register_autograd(_spmm_cols_bwd, setup_context=_spmm_cols_setup)
+
+
+# ============================================================================ edge weights
+# PyG GCNConv.forward(x, edge_index, edge_weight): the weighted gcn_norm as a differentiable op
+# over the structure of a weighted GCNGraph (ops.GCNGraph.build(..., edge_weight=...)), and the
+# sampled dense-dense product the propagates' dL/dw is made of.
+@torch.library.custom_op(f"{NS}::sddmm_cols", mutates_args=(), device_types="cuda")
+def sddmm_cols(rowptr: Tensor, col: Tensor, a: Tensor, b: Tensor) -> Tensor:
+    """out[k] = a[row(k)] . b[col[k]] for every CSR slot k (lg_sddmm_cols); a, b [N][C], any C.
+    out has col's length, zero past rowptr[N].  No autograd: it is what the backwards of
+    gcn_conv and spmm_cols return as dL/dw."""
+    lib = load_library()
+    a, b = _c(a), _c(b)
+    _req(a, b)
+    N, C = a.shape
+    if b.shape != a.shape or rowptr.numel() != N + 1:
+        raise ValueError(f"sddmm_cols: a {tuple(a.shape)}, b {tuple(b.shape)}, rowptr {tuple(rowptr.shape)}")
+    out = torch.zeros(col.numel(), device=a.device, dtype=torch.float32)
+    with _timed("sddmm_cols", a.device):
+        check(lib.lg_sddmm_cols(ptr(rowptr), ptr(col), ptr(a), C, ptr(b), C, ptr(out), N, C, stream_of(a)),
+              "lg_sddmm_cols")
+    return out
+
+
+@sddmm_cols.register_fake
+def _(rowptr, col, a, b):
+    return a.new_empty(col.shape[0])
+
+
+@torch.library.custom_op(f"{NS}::gcn_edge_norm", mutates_args=(), device_types="cuda")
+def gcn_edge_norm(edge_weight: Tensor, rowptr: Tensor, col: Tensor, eid: Tensor, rowptr_t: Tensor, col_t: Tensor,
+                  eid_t: Tensor, normalize: bool, fill: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """(w, w_t, dis) of PyG's weighted gcn_norm over a built structure (lg_graph_reweight):
+    deg summed per row in edge order, dis = deg^-1/2, w = (dis[src] * weight) * dis[dst]; a loop
+    slot takes its supplying self-loop edge's weight or `fill` (eid = -1).  Kernel launches
+    only.  The gradient flows through w (w_t holds the same numbers in the other order)."""
+    lib = load_library()
+    edge_weight = _c(edge_weight)
+    _req(edge_weight)
+    E, N, cap = edge_weight.numel(), rowptr.numel() - 1, col.numel()
+    w = torch.zeros(cap, device=col.device, dtype=torch.float32)
+    w_t = torch.zeros(cap, device=col.device, dtype=torch.float32)
+    dis = torch.empty(N, device=col.device, dtype=torch.float32)
+    check(lib.lg_graph_reweight(ptr(rowptr), ptr(col), ptr(eid), ptr(rowptr_t), ptr(col_t), ptr(eid_t),
+                                ptr(edge_weight) if E else None, E, N, int(normalize), fill, ptr(dis), ptr(w), ptr(w_t),
+                                stream_of(col)), "lg_graph_reweight")
+    return w, w_t, dis
+
+
+@gcn_edge_norm.register_fake
+def _(edge_weight, rowptr, col, eid, rowptr_t, col_t, eid_t, normalize, fill):
+    return (edge_weight.new_empty(col.shape[0]), edge_weight.new_empty(col.shape[0]),
+            edge_weight.new_empty(rowptr.shape[0] - 1))
+
+
+@torch.library.custom_op(f"{NS}::gcn_edge_norm_backward", mutates_args=(), device_types="cuda")
+def gcn_edge_norm_backward(dw: Tensor, edge_weight: Tensor, dis: Tensor, rowptr: Tensor, col: Tensor, eid: Tensor,
+                           rowptr_t: Tensor, col_t: Tensor, eid_t: Tensor, normalize: bool, fill: float) -> Tensor:
+    """dL/d edge_weight from dw = dL/dw in CSR order (lg_gcn_norm_bwd: deterministic, no float
+    atomics)."""
+    lib = load_library()
+    dw, edge_weight = _c(dw), _c(edge_weight)
+    _req(dw, edge_weight, dis)
+    E, N = edge_weight.numel(), rowptr.numel() - 1
+    dv = torch.empty(E, device=dw.device, dtype=torch.float32)
+    ws = torch.empty(int(lib.lg_gcn_norm_bwd_workspace_bytes(E, N)), device=dw.device, dtype=torch.uint8)
+    check(lib.lg_gcn_norm_bwd(ptr(dw), ptr(rowptr), ptr(col), ptr(eid), ptr(rowptr_t), ptr(col_t), ptr(eid_t), ptr(dis),
+                              ptr(edge_weight) if E else None, E, N, int(normalize), fill, ptr(dv) if E else None,
+                              ptr(ws), ws.numel(), stream_of(dw)), "lg_gcn_norm_bwd")
+    return dv
+
+
+@gcn_edge_norm_backward.register_fake
+def _(dw, edge_weight, dis, rowptr, col, eid, rowptr_t, col_t, eid_t, normalize, fill):
+    return torch.empty_like(edge_weight)
+
+
+def _edge_norm_setup(ctx, inputs, output):
+    edge_weight, rowptr, col, eid, rowptr_t, col_t, eid_t, normalize, fill = inputs
+    w, w_t, dis = output
+    ctx.mark_non_differentiable(w_t, dis)
+    ctx.set_materialize_grads(False)
+    ctx.norm = (normalize, fill)
+    ctx.save_for_backward(edge_weight, dis, rowptr, col, eid, rowptr_t, col_t, eid_t)
+
+
+def _edge_norm_bwd(ctx, dw, _dw_t, _ddis):
+    if dw is None:
+        return (None,) * 9
+    dv = torch.ops.leakgnn.gcn_edge_norm_backward(dw, *ctx.saved_tensors, *ctx.norm)
+    return (dv,) + (None,) * 8
+
+
+gcn_edge_norm.register_autograd(_edge_norm_bwd, setup_context=_edge_norm_setup)
 
 
 # ============================================================================ mean_pool

@@ -178,12 +178,22 @@ class GCNGraph:
     nodetab: Optional[torch.Tensor] = None    # int32 (2N, 16): node-major kernels' per-node records
     nodetab_t: Optional[torch.Tensor] = None  # same for the transposed CSR
     order: Optional[torch.Tensor] = None      # int32 (N,): their schedule order (reverse Cuthill-McKee)
-
+    # weighted graphs only (build(..., edge_weight=...), lg_graph_build_w):
+    eid: Optional[torch.Tensor] = None      # int32 (cap,): the input edge of each CSR slot (-1: a fill loop)
+    eid_t: Optional[torch.Tensor] = None    # same for the transposed CSR
+    dis: Optional[torch.Tensor] = None      # fp32 (N,): deg^-1/2, kept for the backward
+    edge_weight: Optional[torch.Tensor] = None  # fp32 (E,): the weights w / w_t were computed from
+    normalize: bool = True
+    fill: float = 1.0
 
     @staticmethod
     def build(edge_index: torch.Tensor, num_nodes: int, device: torch.device, add_self_loops: bool = True,
-              normalize: bool = True, improved: bool = False) -> "GCNGraph":
-        """gcn_norm + CSR on the device (lg_graph_build)."""
+              normalize: bool = True, improved: bool = False,
+              edge_weight: Optional[torch.Tensor] = None) -> "GCNGraph":
+        """gcn_norm + CSR on the device (lg_graph_build; with edge_weight, fp32 (E,):
+        lg_graph_build_w, PyG's weighted gcn_norm, which also fills eid / eid_t / dis).  The
+        weighted build carries no gradient: reweight(edge_weight) attaches the weights to
+        autograd (GCNConv calls it when the weights require grad)."""
         lib = load_library()
         _validate_edge_index(edge_index, num_nodes)
         ei = edge_index.to(device=device, dtype=torch.long).contiguous()
@@ -194,12 +204,28 @@ class GCNGraph:
         g = GCNGraph(N, E, torch.empty(N + 1, **i32), torch.empty(cap, **i32), torch.empty(cap, **f32),
                      torch.empty(N + 1, **i32), torch.empty(cap, **i32), torch.empty(cap, **f32))
         g.nnz_cap = cap
-        ws = torch.empty(int(lib.lg_graph_workspace_bytes(E, N)), device=device, dtype=torch.uint8)
         fill = 2.0 if improved else 1.0
-        check(lib.lg_graph_build(ptr(ei), E, N, int(add_self_loops), int(normalize), fill, ptr(g.rowptr),
-                                 ptr(g.col), ptr(g.w), ptr(g.rowptr_t), ptr(g.col_t), ptr(g.w_t), ptr(ws), ws.numel(),
-                                 stream_of(ei)), "lg_graph_build")
-        g._keepalive = (ei, ws)  # freed after the stream consumes them
+        g.normalize, g.fill = bool(normalize), fill
+        if edge_weight is None:
+            ws = torch.empty(int(lib.lg_graph_workspace_bytes(E, N)), device=device, dtype=torch.uint8)
+            check(lib.lg_graph_build(ptr(ei), E, N, int(add_self_loops), int(normalize), fill, ptr(g.rowptr),
+                                     ptr(g.col), ptr(g.w), ptr(g.rowptr_t), ptr(g.col_t), ptr(g.w_t), ptr(ws),
+                                     ws.numel(), stream_of(ei)), "lg_graph_build")
+            g._keepalive = (ei, ws)  # freed after the stream consumes them
+        else:
+            ew = check_edge_weight(edge_weight, E).detach().to(device=device, dtype=torch.float32).contiguous()
+            # slots past rowptr[N] (input self loops leave the edge list) stay defined: no edge, col 0, w 0
+            g.eid, g.eid_t = torch.full((cap,), -1, **i32), torch.full((cap,), -1, **i32)
+            for t in (g.col, g.col_t, g.w, g.w_t):
+                t.zero_()
+            g.dis = torch.empty(N, **f32)
+            g.edge_weight = ew
+            ws = torch.empty(int(lib.lg_graph_build_w_workspace_bytes(E, N)), device=device, dtype=torch.uint8)
+            check(lib.lg_graph_build_w(ptr(ei), ptr(ew) if E else None, E, N, int(add_self_loops), int(normalize), fill,
+                                       ptr(g.rowptr), ptr(g.col), ptr(g.w), ptr(g.eid), ptr(g.rowptr_t), ptr(g.col_t),
+                                       ptr(g.w_t), ptr(g.eid_t), ptr(g.dis), ptr(ws), ws.numel(), stream_of(ei)),
+                  "lg_graph_build_w")
+            g._keepalive = (ei, ws)
         g.pairs = torch.stack([g.col, g.w.view(torch.int32)], dim=1).contiguous()
         g.pairs_t = torch.stack([g.col_t, g.w_t.view(torch.int32)], dim=1).contiguous()
         # node-major schedule order: reverse Cuthill-McKee (host, once per graph), so a tile's
@@ -213,6 +239,43 @@ class GCNGraph:
         check(lib.lg_nm_table_build(ptr(g.rowptr_t), ptr(g.pairs_t), N, ptr(g.order), ptr(g.nodetab_t),
                                     stream_of(ei)), "lg_nm_table_build")
         return g
+
+    def reweight(self, edge_weight: torch.Tensor) -> "GCNGraph":
+        """New weights on the same structure (learned weights change every step, edge_index
+        does not): dis, w and w_t recomputed by leakgnn::gcn_edge_norm (lg_graph_reweight), the
+        pairs and the node tables refreshed IN PLACE.  Device work only: no host sync, no
+        rebuild.  When edge_weight requires grad, the new w carries the autograd edge to it
+        (the formula of gcn_edge_norm; w_t, the pairs and the tables are the same numbers in
+        another order and carry none).  In place means a backward that still needs the OLD
+        tables must run before the next reweight."""
+        if self.eid is None:
+            raise RuntimeError("GCNGraph.reweight needs a weighted build (GCNGraph.build(..., edge_weight=...))")
+        from . import library  # noqa: F401  (registers leakgnn::gcn_edge_norm; it imports this module)
+        lib = load_library()
+        dev = self.rowptr.device
+        ew = check_edge_weight(edge_weight, self.num_edges).to(device=dev, dtype=torch.float32).contiguous()
+        self.w, self.w_t, self.dis = torch.ops.leakgnn.gcn_edge_norm(
+            ew, self.rowptr, self.col, self.eid, self.rowptr_t, self.col_t, self.eid_t, self.normalize, self.fill)
+        self.edge_weight = ew
+        N, st = self.num_nodes, stream_of(self.rowptr)
+        with torch.no_grad():
+            self.pairs[:, 1].copy_(self.w.detach().view(torch.int32))
+            self.pairs_t[:, 1].copy_(self.w_t.detach().view(torch.int32))
+        check(lib.lg_nm_table_build(ptr(self.rowptr), ptr(self.pairs), N, ptr(self.order), ptr(self.nodetab), st),
+              "lg_nm_table_build")
+        check(lib.lg_nm_table_build(ptr(self.rowptr_t), ptr(self.pairs_t), N, ptr(self.order), ptr(self.nodetab_t), st),
+              "lg_nm_table_build")
+        return self
+
+
+def check_edge_weight(edge_weight: torch.Tensor, num_edges: int) -> torch.Tensor:
+    """A floating tensor of shape (E,) (PyG's edge_weight), checked on the host only."""
+    if not torch.is_tensor(edge_weight) or not edge_weight.is_floating_point():
+        raise TypeError(f"edge_weight must be a floating-point tensor, got "
+                        f"{edge_weight.dtype if torch.is_tensor(edge_weight) else type(edge_weight).__name__}")
+    if edge_weight.dim() != 1 or edge_weight.size(0) != num_edges:
+        raise ValueError(f"edge_weight must have shape ({num_edges},), got {tuple(edge_weight.shape)}")
+    return edge_weight
 
 
 @dataclass
