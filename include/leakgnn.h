@@ -706,6 +706,43 @@ int lg_gru_bwd(const float* residual, const float* tfeat, const float* w_ih, con
                int64_t B, int64_t L, int64_t S, int64_t I, int64_t H,
                void* workspace, int64_t ws_bytes, lg_stream_t stream);
 
+/* Stacked GRU layers (nn.GRU(num_layers > 1); added to ABI 26 without a bump: additions only).
+ * One GRU layer over a dense time-major input; layer l >= 1 of a stack reads the h_seq that
+ * layer l - 1 saved (I = H, no copy), layer 0 stays lg_gru_fwd.
+ *   x      : fp32 [L][Nseq][I]
+ *   h_seq  : fp32 [L][Nseq][H] every step's h (required; h_L is its last step)
+ *   gates  : fp32 [L][Nseq][4][H] as lg_gru_fwd, or NULL (inference)
+ *   flags  : LG_F_DROPOUT: inter-layer dropout applied ON READ — the layer consumes
+ *            x_eff[t][q][i] = x[t][q][i] * keep / (1 - p), keep = the counter RNG's decision for
+ *            element index (t * Nseq + q) * I + i under (seed, salt) (LG_SALT_SEED_PTR honoured);
+ *            x itself stays undropped (the layer below needs it for its own backward).
+ * Backward: BPTT from the saved gates with dh_t += dh_seq[t] at every step.
+ *   input  : dense x as above, or x == NULL and (residual, tfeat, B, S) read as lg_gru_bwd reads
+ *            them (B * S == Nseq, I in {1, 10}, no dropout)
+ *   dh_seq : fp32 [L][Nseq][H] or NULL;  dh_last : fp32 [Nseq][H], added at t = L - 1, or NULL
+ *            (at least one of the two)
+ *   dx     : dense: fp32 [L][Nseq][I], already times the same mask and scale (so it is the
+ *            layer below's dh_seq as is); encoder form: [Nseq][L][I] as lg_gru_bwd; or NULL
+ *   dW_ih (from x_eff), dW_hh, db_ih, db_hh: overwritten, deterministic (per-workgroup slabs,
+ *   fixed-order reduction).  Workspace: lg_gru_seq_bwd_workspace_bytes (covers either input form;
+ *   the generic kernel's slab rows are capped by a 256 MiB budget).
+ * H in {32, 64} with dense I == H: MFMA kernels (forward on the f16x2 split, the x scale taken
+ * from the data per staging chunk; backward on fp32 MFMA).  H in {32, 64} in the encoder form:
+ * lg_gru_bwd's fp32 MFMA kernel.  Any other H, I in 1..1024: generic kernels (one hidden unit
+ * per thread).  LG_EUNSUPPORTED beyond 1024 or for other flags. */
+int lg_gru_seq_fwd(const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
+                   const float* b_hh, float* h_seq, float* gates,
+                   int64_t Nseq, int64_t L, int64_t I, int64_t H,
+                   int flags, float dropout_p, uint64_t seed, uint32_t salt, lg_stream_t stream);
+int64_t lg_gru_seq_bwd_workspace_bytes(int64_t Nseq, int64_t I, int64_t H);
+int lg_gru_seq_bwd(const float* x, const float* residual, const float* tfeat,
+                   const float* w_ih, const float* w_hh, const float* h_seq, const float* gates,
+                   const float* dh_seq, const float* dh_last,
+                   float* dx, float* dw_ih, float* dw_hh, float* db_ih, float* db_hh,
+                   int64_t B, int64_t S, int64_t Nseq, int64_t L, int64_t I, int64_t H,
+                   int flags, float dropout_p, uint64_t seed, uint32_t salt,
+                   void* workspace, int64_t ws_bytes, lg_stream_t stream);
+
 /* The GRU encoder and the node init in one launch each way (ABI 23; the node-major trunk's
  * compressed node init, lg_node_init_bits_fwd, with the sensor projection's backward,
  * lg_sensor_proj_bwd).  Replaces detector.py:60-73 (the shared GRU) followed by :179-190 (h0,

@@ -416,12 +416,15 @@ __device__ __forceinline__ int dg_col(int src, int c) {
     return (c + 16 * ((src >> 4) & 3)) & (GB<H>::RW - 1);
 }
 
-template <int H, bool UT, bool NEED_DX>
+// DHS (a stacked encoder's first layer, lg_gru_seq_bwd): dhS [L][Nseq][H] is added to dh_t at
+// every step (prefetched one step ahead).  Either of dhS / dhL may be NULL (a one-layer stack
+// has dhL only): a NULL one contributes zero.
+template <int H, bool UT, bool NEED_DX, bool DHS = false>
 __global__ void __launch_bounds__(4 * H)
 k_gru_bwd(const float* __restrict__ resid, const float* __restrict__ tfeat, const float* __restrict__ Wih,
           const float* __restrict__ Whh, const float* __restrict__ hs, const float* __restrict__ gates,
           const float* __restrict__ dhL, float* __restrict__ dx, float* __restrict__ slab, uint32_t Nseq, int L,
-          int S, lg_fastdiv fdS) {
+          int S, lg_fastdiv fdS, const float* __restrict__ dhS) {
     using G = GB<H>;
     constexpr int NW = G::NW, I = UT ? 10 : 1, G3 = 3 * H;
     constexpr int SLAB = G3 * H + G3 * I + 2 * G3;
@@ -459,7 +462,15 @@ k_gru_bwd(const float* __restrict__ resid, const float* __restrict__ tfeat, cons
         for (int k = 0; k < 4; ++k) g[k] = valid ? ld4(p + k * H) : zero4();
     };
 
-    f32x4 dh = valid ? ld4(dhL + static_cast<int64_t>(seq) * H + 16 * w + 4 * q) : zero4();
+    f32x4 dh;
+    if constexpr (DHS) dh = (valid && dhL) ? ld4(dhL + static_cast<int64_t>(seq) * H + 16 * w + 4 * q) : zero4();
+    else dh = valid ? ld4(dhL + static_cast<int64_t>(seq) * H + 16 * w + 4 * q) : zero4();
+    auto load_ds = [&](int t) -> f32x4 {  // DHS: the upstream gradient of step t for this lane's 4 units
+        if (t < 0 || !valid || !dhS) return zero4();
+        return ld4(dhS + (static_cast<int64_t>(t) * Nseq + seq) * H + 16 * w + 4 * q);
+    };
+    f32x4 ds_n = zero4();
+    if constexpr (DHS) ds_n = load_ds(L - 1);
     f32x4 dwh[3][NW], dwx[3], dbhn = zero4();
 #pragma unroll
     for (int gi = 0; gi < 3; ++gi) {
@@ -490,6 +501,10 @@ k_gru_bwd(const float* __restrict__ resid, const float* __restrict__ tfeat, cons
         // (a) elementwise gate backward for this lane's 4 units
         const f32x4 hp = ld4(&hl[t % 3][j * G::HS + 16 * w + 4 * q]);
         const f32x4 r = g_cur[0], z = g_cur[1], n = g_cur[2], hnp = g_cur[3];
+        if constexpr (DHS) {
+            dh += ds_n;
+            ds_n = load_ds(t - 1);
+        }
         f32x4 gr, gz, ghn, gin, dhp;
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
@@ -1258,7 +1273,7 @@ int launch_bwd(bool ut, bool need_dx, const float* residual, const float* tfeat,
     const lg_fastdiv fdS = lg_make_fastdiv(static_cast<uint32_t>(S));
 #define LG_GRU_BWD(UT, DX)                                                                                       \
     lg_launch(k_gru_bwd<H, UT, DX>, grid, 4 * H, 0, s, residual, tfeat, w_ih, w_hh, h_seq, gates, dh_last, dx, slab,   \
-                                                 Nseq, static_cast<int>(L), static_cast<int>(S), fdS)
+                                                 Nseq, static_cast<int>(L), static_cast<int>(S), fdS, nullptr)
 #define LG_GRU_BWD2(UT, F, DF)                                                                                   \
     lg_launch(k_gru_bwd2<H, UT, F, DF>, static_cast<unsigned>(nblocks_seq2(B * S)), GB2<H>::NTH, 0, s, residual,    \
               tfeat, w_hh, h_seq, gates, dh_last, slab, Nseq, static_cast<int>(L), static_cast<int>(S), fdS, GruNiB{})
@@ -1432,6 +1447,581 @@ __global__ void __launch_bounds__(kGenMaxH) k_gru_gen_bwd(const float* __restric
         }
         __syncthreads();
     }
+}
+
+// ------------------------------------------------------------------ stacked layers (dense input)
+// A GRU layer over a dense time-major input x [L][Nseq][I] (lg_gru_seq_fwd / lg_gru_seq_bwd):
+// layer l >= 1 of a stacked encoder reads the h_seq [L][Nseq][H] that layer l - 1 saved, so
+// I = H and no copy is made.  Saved layouts are the first layer's (h_seq, gates above).
+// Inter-layer dropout is applied on read: the layer consumes
+//   x_eff[t][seq][i] = x[t][seq][i] * keep((t * Nseq + seq) * I + i) / (1 - p)
+// (lg_keep of the call's key), the backward forms dW_ih from the same x_eff and writes dx
+// already multiplied by that mask and scale; no dropped copy of x exists.
+struct SeqDrop {
+    int on;
+    float p, scale;
+    uint64_t seed;
+    uint32_t salt;
+};
+__device__ __forceinline__ float seq_drop(const SeqDrop& d, uint32_t key, float v, uint64_t idx) {
+    return d.on ? lg_dropout(v, d.p, d.scale, key, idx) : v;
+}
+__device__ __forceinline__ f32x4 seq_drop4(const SeqDrop& d, uint32_t key, f32x4 v, uint64_t idx) {
+    if (d.on) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = lg_dropout(v[i], d.p, d.scale, key, idx + i);
+    }
+    return v;
+}
+
+// Forward, H in {32, 64}, I == H.  k_gru_fwd's wave roles, recurrence and exchanges (one wave
+// per 16-row gate tile, W_hh h on the f16x2 split at the fixed 2^14 scale of h, two barriers
+// per step); the input product W_ih x_t has K = H here and runs on the same f16x2 MFMAs, off
+// the step's critical path: x is staged kLX steps at a time as split f16 parts in the B
+// operand's lane-major layout, and the product of step t + 1 is issued while the wave would
+// otherwise wait (the r / z waves after barrier (A), the n waves before it).  The x scale is
+// not assumed: each chunk takes the workgroup's max |x_eff| (one LDS max, one extra barrier
+// per chunk), so any dense input and any dropout scale 1 / (1 - p) keep the split's accuracy.
+// The next chunk's rows are loaded into registers while the current one runs.
+constexpr int kLX = 6;  // staging chunk (steps): one (step, K chunk, lane) item per thread
+template <int H, bool SAVE>
+__global__ void __launch_bounds__(12 * H)
+k_gru_seq_fwd(const float* __restrict__ x, const float* __restrict__ Wih, const float* __restrict__ Whh,
+              const float* __restrict__ bih, const float* __restrict__ bhh, float* __restrict__ hs,
+              float* __restrict__ gates, uint32_t Nseq, int L, SeqDrop dr) {
+    constexpr int NU = H / 16, NC = H / 32;
+    static_assert(kLX * NC * 64 == 12 * H, "one staging item per thread");
+    __shared__ __attribute__((aligned(16))) lg_u32x4 xsp[kLX][2][NC][64];  // x split parts: [step][part][chunk][lane]
+    __shared__ __attribute__((aligned(16))) f32x4 grz[2][NU][64];
+    __shared__ __attribute__((aligned(16))) lg_u32x4 hbs[2][NC][64];
+    __shared__ __attribute__((aligned(16))) float bhn[H];
+    __shared__ uint32_t xmax[2];  // float bits of the chunk's max |x_eff| (double-buffered)
+    static_assert(sizeof(xsp) + sizeof(grz) + sizeof(hbs) + sizeof(bhn) + sizeof(xmax) <= 80 * 1024,
+                  "LDS budget: at most half of a CU's 160 KiB");
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = w / NU, u = w % NU;
+    const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
+    const uint32_t seq0 = blockIdx.x * TS, seq = seq0 + j;
+    const bool valid = seq < Nseq;
+    const uint32_t key = dr.on ? lg_dropout_key_dev(dr.seed, dr.salt) : 0u;
+
+    const int row = g * H + 16 * u + j;
+    lg_f16x8 ah[NC][2], ai[NC][2];
+    float hunsc;   // 2^-(sWh + 14)
+    int sWi;       // W_ih's scale exponent (this wave's 16 rows)
+    {
+        f32x4 v[NC][2], vi[NC][2];
+        float m = 0.f, mi = 0.f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                v[c][0][p] = Whh[row * H + 32 * c + 4 * q + p];
+                v[c][1][p] = Whh[row * H + 32 * c + 16 + 4 * q + p];
+                vi[c][0][p] = Wih[row * H + 32 * c + 4 * q + p];
+                vi[c][1][p] = Wih[row * H + 32 * c + 16 + 4 * q + p];
+                m = fmaxf(m, fmaxf(fabsf(v[c][0][p]), fabsf(v[c][1][p])));
+                mi = fmaxf(mi, fmaxf(fabsf(vi[c][0][p]), fabsf(vi[c][1][p])));
+            }
+        }
+        const int sW = lg_f16_scale_exp_c(lg_wave_max_bits(__float_as_uint(m)));
+        sWi = lg_f16_scale_exp_c(lg_wave_max_bits(__float_as_uint(mi)));
+        const float sc = lg_pow2f(sW), sci = lg_pow2f(sWi);
+        hunsc = lg_pow2f(-(sW + 14));
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            split2_f16_x8(v[c][0] * sc, v[c][1] * sc, ah[c][0], ah[c][1]);
+            split2_f16_x8(vi[c][0] * sci, vi[c][1] * sci, ai[c][0], ai[c][1]);
+        }
+    }
+    // biases of the lane's output rows (units 16u + 4q + reg): r, z both, n the x side's
+    // (b_hn joins W_hn h: it is multiplied by r)
+    f32x4 bias;
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+        const int rr = g * H + 16 * u + 4 * q + reg;
+        bias[reg] = g < 2 ? bih[rr] + bhh[rr] : bih[rr];
+    }
+    for (int i = threadIdx.x; i < H; i += blockDim.x) bhn[i] = bhh[2 * H + i];
+    if (threadIdx.x == 0) xmax[0] = xmax[1] = 0u;
+    f32x4 hcur = zero4();
+    if (g == 2) {  // h_{-1} = 0
+        lg_u32x2* dst = reinterpret_cast<lg_u32x2*>(&hbs[0][u >> 1][lane]) + (u & 1);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) dst[2 * NC * 64 * p] = lg_u32x2{0u, 0u};
+    }
+
+    // staging item of this thread: step w / NC of the chunk, K chunk w % NC, this lane's 8 values
+    // x[t][seq][32c + 4q + 0..3], x[t][seq][32c + 16 + 4q + 0..3] (the B operand's k order)
+    const int stt = w / NC, sc_ = w % NC;
+    f32x4 xu, xv;
+    auto load_chunk = [&](int t0) {
+        const int t = t0 + stt;
+        xu = xv = zero4();
+        if (t < L && valid) {
+            const uint64_t e = (static_cast<uint64_t>(t) * Nseq + seq) * H + 32 * sc_ + 4 * q;
+            xu = seq_drop4(dr, key, ld4(x + e), e);
+            xv = seq_drop4(dr, key, ld4(x + e + 16), e + 16);
+        }
+    };
+    float xunsc = 0.f;  // 2^-(sWi + sx) of the chunk in LDS
+    auto xprod = [&](int tt) -> f32x4 {
+        f32x4 xp = zero4();
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            lg_f16x8 xf[2];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) xf[p] = __builtin_bit_cast(lg_f16x8, xsp[tt][p][c][lane]);
+            xp = mfma_f16x2(ai[c], xf, xp);
+        }
+        return xp * xunsc + bias;
+    };
+    load_chunk(0);
+    __syncthreads();  // xmax zeroed, h_{-1} and b_hn posted
+    int par = 0;
+    for (int t0 = 0; t0 < L; t0 += kLX) {
+        const int nt = min(kLX, L - t0);
+        {   // publish the chunk held in (xu, xv); every read of the previous chunk ended before the
+            // last step's barrier (B)
+            float m = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) m = fmaxf(m, fmaxf(fabsf(xu[i]), fabsf(xv[i])));
+            const uint32_t mb = lg_wave_max_bits(__float_as_uint(m));
+            if (lane == 0) atomicMax(&xmax[par], mb);
+            __syncthreads();
+            const int sx = lg_f16_scale_exp_c(xmax[par]);
+            const float sc = lg_pow2f(sx);
+            xunsc = lg_pow2f(-(sWi + sx));
+            lg_f16x8 f0, f1;
+            split2_f16_x8(xu * sc, xv * sc, f0, f1);
+            xsp[stt][0][sc_][lane] = __builtin_bit_cast(lg_u32x4, f0);
+            xsp[stt][1][sc_][lane] = __builtin_bit_cast(lg_u32x4, f1);
+            if (threadIdx.x == 0) xmax[par ^ 1] = 0u;  // next chunk's slot: last read a chunk ago
+            par ^= 1;
+            __syncthreads();
+        }
+        if (t0 + kLX < L) load_chunk(t0 + kLX);
+        f32x4 acur = xprod(0), anext = zero4();
+        for (int tt = 0; tt < nt; ++tt) {
+            const int t = t0 + tt;
+            f32x4 hp = zero4();
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                lg_f16x8 hf[2];
+#pragma unroll
+                for (int p = 0; p < 2; ++p) hf[p] = __builtin_bit_cast(lg_f16x8, hbs[p][c][lane]);
+                hp = mfma_f16x2(ah[c], hf, hp);
+            }
+            hp *= hunsc;
+            if (g < 2) {
+                f32x4 sg;
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) sg[reg] = sigm(acur[reg] + hp[reg]);
+                grz[g][u][lane] = sg;
+                if (SAVE && valid)
+                    st4_act<LG_GRU_AUX>(lg_act_rsrc(gates + static_cast<int64_t>(t) * Nseq * 4 * H, static_cast<int64_t>(Nseq) * 4 * H),
+                            seq * 4 * H + g * H + 16 * u + 4 * q, sg);
+            } else if (tt + 1 < nt) {
+                anext = xprod(tt + 1);  // the n waves would wait for sigma(r), sigma(z) here
+            }
+            __syncthreads();  // (A)
+            if (g == 2) {
+                hp += *reinterpret_cast<const f32x4*>(&bhn[16 * u + 4 * q]);
+                const f32x4 r = grz[0][u][lane], z = grz[1][u][lane];
+                f32x4 n;
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    n[reg] = gru_tanh(acur[reg] + r[reg] * hp[reg]);
+                    hcur[reg] = (1.f - z[reg]) * n[reg] + z[reg] * hcur[reg];
+                }
+                if (valid) {
+                    st4_act<LG_GRU_AUX>(lg_act_rsrc(hs + static_cast<int64_t>(t) * Nseq * H, static_cast<int64_t>(Nseq) * H),
+                            seq * H + 16 * u + 4 * q, hcur);
+                    if constexpr (SAVE) {
+                        const __amdgpu_buffer_rsrc_t gr =
+                            lg_act_rsrc(gates + static_cast<int64_t>(t) * Nseq * 4 * H, static_cast<int64_t>(Nseq) * 4 * H);
+                        st4_act<LG_GRU_AUX>(gr, seq * 4 * H + 2 * H + 16 * u + 4 * q, n);
+                        st4_act<LG_GRU_AUX>(gr, seq * 4 * H + 3 * H + 16 * u + 4 * q, hp);
+                    }
+                }
+                const f32x4 hsc = hcur * 16384.f;
+                uint32_t a0, a1, b0, b1;
+                split2_pair_mix(hsc[0], hsc[1], a0, a1);
+                split2_pair_mix(hsc[2], hsc[3], b0, b1);
+                lg_u32x2* dst = reinterpret_cast<lg_u32x2*>(&hbs[0][u >> 1][lane]) + (u & 1);
+                dst[0] = lg_u32x2{a0, b0};
+                dst[2 * NC * 64] = lg_u32x2{a1, b1};
+            } else if (tt + 1 < nt) {
+                anext = xprod(tt + 1);  // the r / z waves wait for h_t here
+            }
+            __syncthreads();  // (B)
+            acur = anext;
+        }
+    }
+}
+
+// Backward, H in {32, 64}, I == H: k_gru_bwd's structure (one workgroup = 16 sequences x H/16
+// waves, exact v_mfma_f32_16x16x4_f32 for every product, one barrier per step) with
+//  - dh_t += dhS[t] at every step (the layer above's dx), dh_last optional;
+//  - x_t (with the dropout mask and scale) staged as a second [seq][H] tile beside h_{t-1},
+//    prefetched two steps ahead the same way, so dW_ih (3H x H) accumulates like dW_hh;
+//  - dx_t = W_ih^T dG_i,t on a second set of A fragments, every wave its 16 units, written
+//    [L][Nseq][H] times the same mask and scale;
+//  - the bias gradients as per-lane sums folded over the 16 sequence lanes at the end.
+// fp32 MFMA, not the f16x2 split of k_gru_bwd2: that kernel's per-step scale bound assumes
+// dh_t = z dh_{t+1} + W_hh^T dG and a per-step upstream term does not enter it.
+template <int H, bool DX>
+__global__ void __launch_bounds__(4 * H)
+k_gru_seq_bwd(const float* __restrict__ x, const float* __restrict__ Wih, const float* __restrict__ Whh,
+              const float* __restrict__ hs, const float* __restrict__ gates, const float* __restrict__ dhS,
+              const float* __restrict__ dhL, float* __restrict__ dx, float* __restrict__ slab, uint32_t Nseq, int L,
+              SeqDrop dr) {
+    using G = GB<H>;
+    constexpr int NW = G::NW, G3 = 3 * H;
+    constexpr int SLAB = G3 * H + G3 * H + 2 * G3;
+    __shared__ __attribute__((aligned(16))) float hl[3][TS * G::HS];
+    __shared__ __attribute__((aligned(16))) float xl[3][TS * G::HS];
+    __shared__ __attribute__((aligned(16))) float dg[2][64 * G::DS];
+    static_assert(sizeof(hl) + sizeof(xl) + sizeof(dg) <= 80 * 1024, "LDS budget: at most half of a CU's 160 KiB");
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
+    const uint32_t seq0 = blockIdx.x * TS, seq = seq0 + j;
+    const bool valid = seq < Nseq;
+    const uint32_t seqc = valid ? seq : 0u;
+    const uint32_t key = dr.on ? lg_dropout_key_dev(dr.seed, dr.salt) : 0u;
+
+    // W_hh^T and W_ih^T fragments: A[row j = unit 16w + j][k = gate row fk(ks, q)]
+    float at[G::KG], ai[DX ? G::KG : 1];
+#pragma unroll
+    for (int ks = 0; ks < G::KG; ++ks) {
+        at[ks] = Whh[fk(ks, q) * H + 16 * w + j];
+        if constexpr (DX) ai[ks] = Wih[fk(ks, q) * H + 16 * w + j];
+    }
+
+    const int hrow = threadIdx.x / (H / 4), hc4 = threadIdx.x % (H / 4);
+    const uint32_t hseq = seq0 + hrow;
+    const bool hvalid = hseq < Nseq;
+    auto load_h = [&](int t) -> f32x4 {
+        if (t < 0 || !hvalid) return zero4();
+        return ld4(hs + (static_cast<int64_t>(t) * Nseq + hseq) * H + 4 * hc4);
+    };
+    auto load_x = [&](int t) -> f32x4 {  // x_eff row piece of step t
+        if (t < 0 || !hvalid) return zero4();
+        const uint64_t e = (static_cast<uint64_t>(t) * Nseq + hseq) * H + 4 * hc4;
+        return seq_drop4(dr, key, ld4(x + e), e);
+    };
+    auto load_g = [&](int t, f32x4 (&gv)[4]) {
+        const float* p = gates + (static_cast<int64_t>(t) * Nseq + seqc) * 4 * H + 16 * w + 4 * q;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gv[k] = valid ? ld4(p + k * H) : zero4();
+    };
+    auto load_ds = [&](int t) -> f32x4 {
+        if (t < 0 || !valid || !dhS) return zero4();
+        return ld4(dhS + (static_cast<int64_t>(t) * Nseq + seq) * H + 16 * w + 4 * q);
+    };
+
+    f32x4 dh = (valid && dhL) ? ld4(dhL + static_cast<int64_t>(seq) * H + 16 * w + 4 * q) : zero4();
+    f32x4 dwh[3][NW], dwx[3][NW], db[4] = {zero4(), zero4(), zero4(), zero4()};  // db: r, z, hn, in
+#pragma unroll
+    for (int gi = 0; gi < 3; ++gi)
+#pragma unroll
+        for (int nt = 0; nt < NW; ++nt) dwh[gi][nt] = dwx[gi][nt] = zero4();
+
+    f32x4 g_cur[4], g_n1[4];
+    load_g(L - 1, g_cur);
+    if (L >= 2) load_g(L - 2, g_n1);
+    f32x4 h_n1 = load_h(L - 3), h_n2 = load_h(L - 4);
+    f32x4 x_n1 = load_x(L - 2), x_n2 = load_x(L - 3);
+    f32x4 ds_n = load_ds(L - 1);
+    st4(&hl[(L - 1) % 3][hrow * G::HS + 4 * hc4], load_h(L - 2));
+    st4(&xl[(L - 1) % 3][hrow * G::HS + 4 * hc4], load_x(L - 1));
+    __syncthreads();
+
+    for (int t = L - 1; t >= 0; --t) {
+        // hl[t%3] = h_{t-1} and xl[t%3] = x_t were published by the previous barrier; slot
+        // (t-1)%3 and dg[t&1] were last read two steps ago
+        if (t >= 1) {
+            st4(&hl[(t - 1) % 3][hrow * G::HS + 4 * hc4], h_n1);
+            st4(&xl[(t - 1) % 3][hrow * G::HS + 4 * hc4], x_n1);
+        }
+        const f32x4 hp = ld4(&hl[t % 3][j * G::HS + 16 * w + 4 * q]);
+        const f32x4 r = g_cur[0], z = g_cur[1], n = g_cur[2], hnp = g_cur[3];
+        dh += ds_n;
+        ds_n = load_ds(t - 1);
+        f32x4 gr, gz, ghn, gin, dhp;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const float d = dh[reg];
+            const float dn = d * (1.f - z[reg]);
+            const float dzv = d * (hp[reg] - n[reg]);
+            dhp[reg] = d * z[reg];
+            const float dnp = dn * (1.f - n[reg] * n[reg]);
+            gin[reg] = dnp;
+            ghn[reg] = dnp * r[reg];
+            gr[reg] = dnp * hnp[reg] * r[reg] * (1.f - r[reg]);
+            gz[reg] = dzv * z[reg] * (1.f - z[reg]);
+        }
+        db[0] += gr;
+        db[1] += gz;
+        db[2] += ghn;
+        db[3] += gin;
+        float* dgb = dg[t & 1];
+        st4(&dgb[lane * G::DS + dg_col<H>(lane, 4 * (0 * NW + w))], gr);
+        st4(&dgb[lane * G::DS + dg_col<H>(lane, 4 * (1 * NW + w))], gz);
+        st4(&dgb[lane * G::DS + dg_col<H>(lane, 4 * (2 * NW + w))], ghn);
+        st4(&dgb[lane * G::DS + dg_col<H>(lane, 4 * (3 * NW + w))], gin);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) g_cur[k] = g_n1[k];
+        if (t >= 2) load_g(t - 2, g_n1);
+        h_n1 = h_n2;
+        h_n2 = load_h(t - 4);
+        x_n1 = x_n2;
+        x_n2 = load_x(t - 3);
+        __syncthreads();  // dG of all waves visible
+
+        f32x4 acc[4] = {zero4(), zero4(), zero4(), zero4()};
+#pragma unroll
+        for (int a = 0; a < G::KG / 4; ++a) {
+            const f32x4 bv = ld4(&dgb[lane * G::DS + dg_col<H>(lane, 4 * a)]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i] = mfma(at[4 * a + i], bv[i], acc[i]);
+        }
+        dh = dhp + ((acc[0] + acc[1]) + (acc[2] + acc[3]));
+
+        if constexpr (DX) {
+            // dx_t^T[unit][seq] = sum_g W_ih[g][unit] dG_i[g][seq]   (gates r, z, in: the hn block skipped)
+            f32x4 xa[4] = {zero4(), zero4(), zero4(), zero4()};
+#pragma unroll
+            for (int a = 0; a < G::KG / 4; ++a) {
+                const int ca = a < 2 * NW ? a : a + NW;
+                const f32x4 bv = ld4(&dgb[lane * G::DS + dg_col<H>(lane, 4 * ca)]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) xa[i] = mfma(ai[4 * a + i], bv[i], xa[i]);
+            }
+            if (valid) {
+                const uint64_t e = (static_cast<uint64_t>(t) * Nseq + seq) * H + 16 * w + 4 * q;
+                f32x4 v = (xa[0] + xa[1]) + (xa[2] + xa[3]);
+                if (dr.on) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) v[i] = lg_dropout(v[i], dr.p, dr.scale, key, e + i);
+                }
+                st4(dx + e, v);
+            }
+        }
+
+        // dW over this step's 16 sequences
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const int src = (4 * ks + q) + 16 * (j >> 2);
+            const float* rowp = &dgb[src * G::DS];
+            const float a0 = rowp[dg_col<H>(src, 4 * (0 * NW + w) + (j & 3))];
+            const float a1 = rowp[dg_col<H>(src, 4 * (1 * NW + w) + (j & 3))];
+            const float a2 = rowp[dg_col<H>(src, 4 * (2 * NW + w) + (j & 3))];
+            const float a3 = rowp[dg_col<H>(src, 4 * (3 * NW + w) + (j & 3))];
+            const float* hrow_p = &hl[t % 3][(4 * ks + q) * G::HS];
+            const float* xrow_p = &xl[t % 3][(4 * ks + q) * G::HS];
+#pragma unroll
+            for (int nt = 0; nt < NW; ++nt) {
+                const float hb = hrow_p[16 * nt + j], xb = xrow_p[16 * nt + j];
+                dwh[0][nt] = mfma(a0, hb, dwh[0][nt]);
+                dwh[1][nt] = mfma(a1, hb, dwh[1][nt]);
+                dwh[2][nt] = mfma(a2, hb, dwh[2][nt]);
+                dwx[0][nt] = mfma(a0, xb, dwx[0][nt]);
+                dwx[1][nt] = mfma(a1, xb, dwx[1][nt]);
+                dwx[2][nt] = mfma(a3, xb, dwx[2][nt]);
+            }
+        }
+    }
+
+    float* out = slab + static_cast<int64_t>(blockIdx.x) * SLAB;
+    float* oWhh = out;
+    float* oWih = out + G3 * H;
+    float* obih = oWih + G3 * H;
+    float* obhh = obih + G3;
+#pragma unroll
+    for (int gi = 0; gi < 3; ++gi)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int g = gi * H + 16 * w + 4 * q + reg;
+#pragma unroll
+            for (int nt = 0; nt < NW; ++nt) {
+                oWhh[g * H + 16 * nt + j] = dwh[gi][nt][reg];
+                oWih[g * H + 16 * nt + j] = dwx[gi][nt][reg];
+            }
+        }
+    // bias gradients: fold the 16 sequence lanes of each row
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) db[k][reg] += __shfl_xor(db[k][reg], off);
+    if (j == 0) {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const int uu = 16 * w + 4 * q + reg;
+            obih[uu] = obhh[uu] = db[0][reg];
+            obih[H + uu] = obhh[H + uu] = db[1][reg];
+            obih[2 * H + uu] = db[3][reg];
+            obhh[2 * H + uu] = db[2][reg];
+        }
+    }
+}
+
+// Any H in 1..1024 and any dense I in 1..1024, and the encoder input form (x == NULL: x_t =
+// [residual[b, t, s], tfeat[b, t, :]], I in {1, 10}, dx [Nseq][L][I]) at widths off the tiled
+// kernels: k_gru_gen_fwd / k_gru_gen_bwd's scheme (a workgroup per sequence, a hidden unit per
+// thread, input columns strided over the threads), 64-bit offsets throughout.
+__global__ void __launch_bounds__(kGenMaxH) k_gru_seq_gen_fwd(const float* __restrict__ x,
+                                                              const float* __restrict__ w_ih,
+                                                              const float* __restrict__ w_hh,
+                                                              const float* __restrict__ b_ih,
+                                                              const float* __restrict__ b_hh, float* __restrict__ h_seq,
+                                                              float* __restrict__ gates, int64_t nseq, int L, int I, int H,
+                                                              SeqDrop dr) {
+    extern __shared__ float gsm[];
+    float* hs = gsm;      // h_{t-1} [H]
+    float* xs = gsm + H;  // x_eff,t [I]
+    const int u = threadIdx.x, nth = blockDim.x;
+    const uint32_t key = dr.on ? lg_dropout_key_dev(dr.seed, dr.salt) : 0u;
+    for (int64_t seq = blockIdx.x; seq < nseq; seq += gridDim.x) {
+        if (u < H) hs[u] = 0.f;
+        for (int t = 0; t < L; ++t) {
+            const int64_t r = static_cast<int64_t>(t) * nseq + seq;
+            for (int i = u; i < I; i += nth) xs[i] = seq_drop(dr, key, x[r * I + i], static_cast<uint64_t>(r) * I + i);
+            __syncthreads();
+            float hn = 0.f, g[4] = {0.f, 0.f, 0.f, 0.f};
+            if (u < H) {
+                float a[3], c[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const int row = k * H + u;
+                    a[k] = b_ih[row];
+                    const float* wi = w_ih + static_cast<int64_t>(row) * I;
+                    for (int i = 0; i < I; ++i) a[k] = fmaf(wi[i], xs[i], a[k]);
+                    c[k] = b_hh[row];
+                    const float* wr = w_hh + static_cast<int64_t>(row) * H;
+                    for (int i = 0; i < H; ++i) c[k] = fmaf(wr[i], hs[i], c[k]);
+                }
+                g[0] = sigm(a[0] + c[0]);
+                g[1] = sigm(a[1] + c[1]);
+                g[2] = gru_tanh(a[2] + g[0] * c[2]);
+                g[3] = c[2];
+                hn = (1.f - g[1]) * g[2] + g[1] * hs[u];
+            }
+            __syncthreads();
+            if (u < H) {
+                hs[u] = hn;
+                h_seq[r * H + u] = hn;
+                if (gates) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) gates[(r * 4 + k) * H + u] = g[k];
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(kGenMaxH) k_gru_seq_gen_bwd(
+    const float* __restrict__ x, const float* __restrict__ residual, const float* __restrict__ tfeat,
+    const float* __restrict__ w_ih, const float* __restrict__ w_hh, const float* __restrict__ h_seq,
+    const float* __restrict__ gates, const float* __restrict__ dh_seq, const float* __restrict__ dh_last,
+    float* __restrict__ dx, float* __restrict__ slab, int64_t nseq, int L, int S, int I, int H, SeqDrop dr) {
+    extern __shared__ float gsm[];
+    float* dh = gsm;            // dL/dh_t [H]
+    float* hp = dh + H;         // h_{t-1} [H]
+    float* dgh = hp + H;        // d(W_h. h + b_h.) [3H]
+    float* dgn = dgh + 3 * H;   // d(W_in x + b_in) [H]
+    float* xs = dgn + H;        // x_eff,t [I]
+    const int u = threadIdx.x, nth = blockDim.x;
+    const int G3 = 3 * H;
+    const int64_t len = static_cast<int64_t>(G3) * (H + I) + 2 * G3;
+    const uint32_t key = dr.on ? lg_dropout_key_dev(dr.seed, dr.salt) : 0u;
+    float* row = slab + blockIdx.x * len;
+    float* dwhh = row;
+    float* dwih = row + static_cast<int64_t>(G3) * H;
+    float* dbih = dwih + static_cast<int64_t>(G3) * I;
+    float* dbhh = dbih + G3;
+    // each element is zeroed, and later accumulated, by one fixed thread
+    if (u < H)
+        for (int j = 0; j < G3; ++j) dwhh[static_cast<int64_t>(j) * H + u] = 0.f;
+    for (int i = u; i < I; i += nth)
+        for (int j = 0; j < G3; ++j) dwih[static_cast<int64_t>(j) * I + i] = 0.f;
+    for (int j = u; j < G3; j += nth) dbih[j] = dbhh[j] = 0.f;
+    auto dgi = [&](int j) { return j < 2 * H ? dgh[j] : dgn[j - 2 * H]; };
+    for (int64_t seq = blockIdx.x; seq < nseq; seq += gridDim.x) {
+        const int64_t b = seq / S, sn = seq % S;  // encoder form only (S = 1 otherwise)
+        if (u < H) dh[u] = dh_last ? dh_last[seq * H + u] : 0.f;
+        for (int t = L - 1; t >= 0; --t) {
+            const int64_t r = static_cast<int64_t>(t) * nseq + seq;
+            for (int i = u; i < I; i += nth) {
+                if (x) xs[i] = seq_drop(dr, key, x[r * I + i], static_cast<uint64_t>(r) * I + i);
+                else xs[i] = i == 0 ? residual[(b * L + t) * S + sn] : tfeat[(b * L + t) * (I - 1) + i - 1];
+            }
+            float dz_keep = 0.f;
+            if (u < H) {
+                const float h0 = t > 0 ? h_seq[(r - nseq) * H + u] : 0.f;
+                hp[u] = h0;
+                const float rg = gates[(r * 4 + 0) * H + u], zg = gates[(r * 4 + 1) * H + u];
+                const float ng = gates[(r * 4 + 2) * H + u], ghn = gates[(r * 4 + 3) * H + u];
+                const float d = dh[u] + (dh_seq ? dh_seq[r * H + u] : 0.f);
+                const float dnp = d * (1.f - zg) * (1.f - ng * ng);
+                const float dzp = d * (h0 - ng) * zg * (1.f - zg);
+                const float drp = dnp * ghn * rg * (1.f - rg);
+                dgh[u] = drp;
+                dgh[H + u] = dzp;
+                dgh[2 * H + u] = dnp * rg;
+                dgn[u] = dnp;
+                dz_keep = d * zg;
+            }
+            __syncthreads();
+            float acc = dz_keep;
+            if (u < H) {
+                for (int j = 0; j < G3; ++j) {
+                    const float gj = dgh[j];
+                    acc = fmaf(w_hh[static_cast<int64_t>(j) * H + u], gj, acc);
+                    dwhh[static_cast<int64_t>(j) * H + u] += gj * hp[u];
+                }
+            }
+            for (int i = u; i < I; i += nth) {
+                float dxi = 0.f;
+                for (int j = 0; j < G3; ++j) {
+                    const float gj = dgi(j);
+                    dxi = fmaf(w_ih[static_cast<int64_t>(j) * I + i], gj, dxi);
+                    dwih[static_cast<int64_t>(j) * I + i] += gj * xs[i];
+                }
+                if (dx) {
+                    if (x) dx[r * I + i] = seq_drop(dr, key, dxi, static_cast<uint64_t>(r) * I + i);
+                    else dx[(seq * L + t) * I + i] = dxi;
+                }
+            }
+            for (int j = u; j < G3; j += nth) {
+                dbih[j] += dgi(j);
+                dbhh[j] += dgh[j];
+            }
+            __syncthreads();
+            if (u < H) dh[u] = acc;
+        }
+        __syncthreads();
+    }
+}
+
+// Slab rows of lg_gru_seq_bwd (workspace query and launch alike).  The tiled kernels write one
+// row per 16-sequence workgroup; the generic kernel's grid is capped by a byte budget, so the
+// workspace stays bounded at every width (one row is 25 MB at H = I = 1024).
+constexpr int64_t kSeqSlabBudget = int64_t{256} << 20;
+inline int64_t seq_slab_len(int64_t I, int64_t H) { return 3 * H * (H + I) + 6 * H; }
+inline bool seq_tiled(bool dense, int64_t I, int64_t H) {
+    return (H == 32 || H == 64) && (dense ? I == H : (I == 1 || I == 10));
+}
+inline int64_t seq_bwd_rows(bool tiled, int64_t Nseq, int64_t I, int64_t H) {
+    if (tiled) return std::max<int64_t>(1, nblocks_seq(Nseq));
+    const int64_t fit = kSeqSlabBudget / (seq_slab_len(I, H) * static_cast<int64_t>(sizeof(float)));
+    return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(Nseq, kGenBwdBlocks), fit));
+}
+inline bool seq_dims_ok(int64_t Nseq, int64_t L, int64_t I, int64_t H) {
+    return Nseq >= 0 && Nseq < (int64_t{1} << 31) && L > 0 && L <= INT32_MAX && I > 0 && H > 0;
 }
 
 bool dims_ok(int64_t B, int64_t L, int64_t S) {
@@ -1620,4 +2210,115 @@ extern "C" int lg_gru_node_init_bwd(const float* residual, const float* tfeat, c
     const LgSlabSeg segs[6] = {{0, nWhh, dw_hh}, {nWhh, nWih, dw_ih}, {nWhh + nWih, G3, db_ih},
                                {nWhh + nWih + G3, G3, db_hh}, {gl, H * (H + 1), dproj_w}, dbseg};
     return lg_launch_slab_reduce_multi(slab, nb, len, segs, 6, nullptr, nullptr, s);
+}
+
+// ------------------------------------------------------------------ stacked layers: entry points
+namespace {
+inline SeqDrop seq_drop_args(int flags, float p, uint64_t seed, uint32_t salt) {
+    const bool on = (flags & LG_F_DROPOUT) != 0 && p > 0.f;
+    return SeqDrop{on ? 1 : 0, p, on ? 1.0f / (1.0f - p) : 1.0f, seed, salt};
+}
+}  // namespace
+
+extern "C" int lg_gru_seq_fwd(const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
+                              const float* b_hh, float* h_seq, float* gates, int64_t Nseq, int64_t L, int64_t I,
+                              int64_t H, int flags, float dropout_p, uint64_t seed, uint32_t salt,
+                              lg_stream_t stream) {
+    if (!seq_dims_ok(Nseq, L, I, H)) return LG_EINVAL;
+    if (!x || !w_ih || !w_hh || !b_ih || !b_hh || !h_seq) return LG_EINVAL;
+    if ((flags & LG_F_DROPOUT) && !(dropout_p >= 0.f && dropout_p < 1.f)) return LG_EINVAL;
+    if (flags & ~LG_F_DROPOUT) return LG_EUNSUPPORTED;
+    if (H > kGenMaxH || I > kGenMaxH) return LG_EUNSUPPORTED;
+    if (Nseq == 0) return LG_OK;
+    hipStream_t s = lg_stream(stream);
+    const SeqDrop dr = seq_drop_args(flags, dropout_p, seed, salt);
+    // the tiled kernel addresses one step's rows of its stores by 32-bit byte offsets: larger
+    // calls run the generic kernel (64-bit offsets)
+    const bool rows32 = Nseq * (gates ? 4 : 1) * H * 4 < (int64_t{1} << 31);
+    if (seq_tiled(true, I, H) && rows32) {
+        const unsigned grid = static_cast<unsigned>(nblocks_seq(Nseq));
+        const uint32_t n = static_cast<uint32_t>(Nseq);
+#define LG_GRU_SEQ_FWD(HH, SV) \
+    lg_launch(k_gru_seq_fwd<HH, SV>, grid, 12 * HH, 0, s, x, w_ih, w_hh, b_ih, b_hh, h_seq, gates, n, static_cast<int>(L), dr)
+        if (H == 64) { if (gates) LG_GRU_SEQ_FWD(64, true); else LG_GRU_SEQ_FWD(64, false); }
+        else { if (gates) LG_GRU_SEQ_FWD(32, true); else LG_GRU_SEQ_FWD(32, false); }
+#undef LG_GRU_SEQ_FWD
+    } else {
+        const unsigned grid = static_cast<unsigned>(std::min<int64_t>(Nseq, 4096));
+        lg_launch(k_gru_seq_gen_fwd, grid, gen_threads(H), sizeof(float) * (H + I), s, x, w_ih, w_hh, b_ih, b_hh, h_seq,
+                  gates, Nseq, static_cast<int>(L), static_cast<int>(I), static_cast<int>(H), dr);
+    }
+    LG_RET_IF_LAUNCH_FAILED();
+    return LG_OK;
+}
+
+extern "C" int64_t lg_gru_seq_bwd_workspace_bytes(int64_t Nseq, int64_t I, int64_t H) {
+    if (Nseq < 0 || I < 1 || I > kGenMaxH || H < 1 || H > kGenMaxH) return LG_EINVAL;
+    // I == H in {32, 64} can only be the dense tiled kernel; I in {1, 10} at those H is the tiled
+    // encoder form or a dense generic call (the form is not known here): the larger of the two
+    int64_t rows = seq_bwd_rows(seq_tiled(true, I, H), Nseq, I, H);
+    if (seq_tiled(false, I, H)) rows = std::max(rows, seq_bwd_rows(true, Nseq, I, H));
+    return rows * seq_slab_len(I, H) * static_cast<int64_t>(sizeof(float));
+}
+
+extern "C" int lg_gru_seq_bwd(const float* x, const float* residual, const float* tfeat, const float* w_ih,
+                              const float* w_hh, const float* h_seq, const float* gates, const float* dh_seq,
+                              const float* dh_last, float* dx, float* dw_ih, float* dw_hh, float* db_ih,
+                              float* db_hh, int64_t B, int64_t S, int64_t Nseq, int64_t L, int64_t I, int64_t H,
+                              int flags, float dropout_p, uint64_t seed, uint32_t salt, void* workspace,
+                              int64_t ws_bytes, lg_stream_t stream) {
+    if (!seq_dims_ok(Nseq, L, I, H)) return LG_EINVAL;
+    const bool dense = x != nullptr;
+    if (!dense && (!residual || B < 0 || S <= 0 || B * S != Nseq || S > INT32_MAX)) return LG_EINVAL;
+    if (!w_ih || !w_hh || !h_seq || !gates || !dw_ih || !dw_hh || !db_ih || !db_hh || !workspace) return LG_EINVAL;
+    if (!dh_seq && !dh_last) return LG_EINVAL;
+    if ((flags & LG_F_DROPOUT) && !(dropout_p >= 0.f && dropout_p < 1.f)) return LG_EINVAL;
+    if (flags & ~LG_F_DROPOUT) return LG_EUNSUPPORTED;
+    if (H > kGenMaxH || I > kGenMaxH) return LG_EUNSUPPORTED;
+    if (!dense && ((I != 1 && I != 10) || (flags & LG_F_DROPOUT))) return LG_EUNSUPPORTED;  // the encoder's input is data
+    if (!dense && I == 10 && !tfeat) return LG_EINVAL;
+    const bool tiled = seq_tiled(dense, I, H);
+    const int nb = static_cast<int>(seq_bwd_rows(tiled, Nseq, I, H));
+    const int64_t len = seq_slab_len(I, H), G3 = 3 * H;
+    if (ws_bytes < nb * len * static_cast<int64_t>(sizeof(float))) return LG_EINVAL;
+    hipStream_t s = lg_stream(stream);
+    float* slab = static_cast<float*>(workspace);
+    const SeqDrop dr = seq_drop_args(flags, dropout_p, seed, salt);
+    if (Nseq == 0) {
+        if (hipMemsetAsync(slab, 0, sizeof(float) * len, s) != hipSuccess) return LG_EHIP;
+    } else if (!tiled) {
+        lg_launch(k_gru_seq_gen_bwd, static_cast<unsigned>(nb), gen_threads(H), sizeof(float) * (6 * H + I), s, x,
+                  residual, tfeat, w_ih, w_hh, h_seq, gates, dh_seq, dh_last, dx, slab, Nseq, static_cast<int>(L),
+                  static_cast<int>(dense ? 1 : S), static_cast<int>(I), static_cast<int>(H), dr);
+        LG_RET_IF_LAUNCH_FAILED();
+    } else if (dense) {
+        const uint32_t n = static_cast<uint32_t>(Nseq);
+#define LG_GRU_SEQ_BWD(HH, DX)                                                                                     \
+    lg_launch(k_gru_seq_bwd<HH, DX>, static_cast<unsigned>(nb), 4 * HH, 0, s, x, w_ih, w_hh, h_seq, gates, dh_seq, \
+              dh_last, dx, slab, n, static_cast<int>(L), dr)
+        if (H == 64) { if (dx) LG_GRU_SEQ_BWD(64, true); else LG_GRU_SEQ_BWD(64, false); }
+        else { if (dx) LG_GRU_SEQ_BWD(32, true); else LG_GRU_SEQ_BWD(32, false); }
+#undef LG_GRU_SEQ_BWD
+        LG_RET_IF_LAUNCH_FAILED();
+    } else {  // the encoder's first layer under a stack: k_gru_bwd with the per-step upstream gradient
+        const uint32_t n = static_cast<uint32_t>(Nseq);
+        const lg_fastdiv fdS = lg_make_fastdiv(static_cast<uint32_t>(S));
+#define LG_GRU_BWD_DHS(HH, UT, DX)                                                                                \
+    lg_launch(k_gru_bwd<HH, UT, DX, true>, static_cast<unsigned>(nb), 4 * HH, 0, s, residual, tfeat, w_ih, w_hh, h_seq, \
+              gates, dh_last, dx, slab, n, static_cast<int>(L), static_cast<int>(S), fdS, dh_seq)
+        const bool ut = I == 10, dxv = dx != nullptr;
+        if (H == 64) {
+            if (ut) { if (dxv) LG_GRU_BWD_DHS(64, true, true); else LG_GRU_BWD_DHS(64, true, false); }
+            else { if (dxv) LG_GRU_BWD_DHS(64, false, true); else LG_GRU_BWD_DHS(64, false, false); }
+        } else {
+            if (ut) { if (dxv) LG_GRU_BWD_DHS(32, true, true); else LG_GRU_BWD_DHS(32, true, false); }
+            else { if (dxv) LG_GRU_BWD_DHS(32, false, true); else LG_GRU_BWD_DHS(32, false, false); }
+        }
+#undef LG_GRU_BWD_DHS
+        LG_RET_IF_LAUNCH_FAILED();
+    }
+    const int64_t nWhh = G3 * H, nWih = G3 * I;
+    const LgSlabSeg segs[4] = {{0, nWhh, dw_hh}, {nWhh, nWih, dw_ih}, {nWhh + nWih, G3, db_ih},
+                               {nWhh + nWih + G3, G3, db_hh}};
+    return lg_launch_slab_reduce_multi(slab, nb, len, segs, 4, nullptr, nullptr, s);
 }

@@ -15,6 +15,10 @@ registered ops of models/library.py (leakgnn::encoder_trunk / gru_encoder / sens
 gnn_trunk / detector_heads) and models/loss.py (leakgnn::cross_entropy):
   * the GRU sensor encoder with the node init (sensor projection, mask column, ReLU,
     dropout) fused into its epilogue, and the projection's backward into the GRU backward;
+    a stacked encoder (LeakDetector(sensor_layers > 1), nn.GRU's num_layers and inter-layer
+    dropout) runs leakgnn::gru_stack instead — layer 0 on the same kernel, the upper layers
+    on the dense-input kernels (lg_gru_seq_fwd / lg_gru_seq_bwd) — followed by gnn_trunk: the
+    fused encoder_trunk op is one-layer only;
   * every GCNConv + ReLU + dropout on the node-major trunk kernels over ONE device-resident
     single-graph CSR (the (2, B*E) batchified edge_index of the reference,
     detector.py:195-196, is never built);
@@ -52,23 +56,34 @@ class SharedSensorGRUEncoder(nn.Module):
 
     def forward(self, r: torch.Tensor, tfeat: Optional[torch.Tensor] = None) -> torch.Tensor:
         """(B, L, S) residuals (+ (B, L, 9) time features) -> (B, S, hidden): h_L of the shared GRU
-        over the B*S sensor sequences, on the fused HIP GRU (lg_gru_fwd / lg_gru_bwd)."""
+        over the B*S sensor sequences, on the fused HIP GRU (lg_gru_fwd / lg_gru_bwd; num_layers > 1:
+        library.gru_stack, the top layer's h_L)."""
         if self.use_time and tfeat is None:
             raise ValueError("tfeat required when use_time=True")
         if not r.is_cuda:
             raise RuntimeError("SharedSensorGRUEncoder runs on a ROCm GPU only (libleakgnn has no CPU path)")
         g = self.gru
-        if g.num_layers != 1 or not 1 <= g.hidden_size <= 1024 or g.bidirectional or not g.bias:
-            raise NotImplementedError("the HIP GRU kernels cover the reference encoder: 1 layer, hidden 1..1024 "
-                                      "(32 / 64 tiled, others generic), bias")
+        if not 1 <= g.hidden_size <= 1024 or g.bidirectional or not g.bias:
+            raise NotImplementedError("the HIP GRU kernels cover unidirectional GRUs with bias, hidden 1..1024 "
+                                      "(32 / 64 tiled, others generic), any number of layers")
         f = ops._f32
-        ws = [f(t) for t in (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0)]
         # contiguous once here: a strided tfeat (a slice of a longer segment) would otherwise be
         # saved as is and copied again in the backward
         tf = f(tfeat).contiguous() if self.use_time else None
         r = f(r)
-        save = torch.is_grad_enabled() and any(t.requires_grad for t in [r, *ws] + ([tf] if tf is not None else []))
-        return torch.ops.leakgnn.gru_encoder(r, tf, *ws, save)[0]
+        if g.num_layers == 1:
+            ws = [f(t) for t in (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0)]
+            save = torch.is_grad_enabled() and any(t.requires_grad
+                                                   for t in [r, *ws] + ([tf] if tf is not None else []))
+            return torch.ops.leakgnn.gru_encoder(r, tf, *ws, save)[0]
+        # stacked: layer 0 as above, the upper layers on the dense-input kernels (library.gru_stack),
+        # dropout between layers in train mode from the library's counter RNG
+        ws = [[f(getattr(g, f"{n}_l{l}")) for l in range(g.num_layers)]
+              for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        save = torch.is_grad_enabled() and any(t.requires_grad for t in [r, *sum(ws, [])] + ([tf] if tf is not None else []))
+        p = float(g.dropout) if self.training else 0.0
+        seed = library.seed_tensor(r.device) if p > 0.0 else _NO_SEED
+        return torch.ops.leakgnn.gru_stack(r, tf, *ws, p, seed, save)[0]
 
 
 class EdgeHead(nn.Module):
@@ -107,7 +122,7 @@ class LeakDetector(nn.Module):
     def __init__(self, inp_path: str | Path, sensor_node_ids: Sequence[str], pipe_ids_in_order: Sequence[str],
                  sensor_hidden: int = 64, node_hidden: int = 64, gnn_layers: int = 2, dropout: float = 0.1,
                  use_time: bool = True, include_links: Sequence[str] = ("PIPES", "PUMPS", "VALVES"),
-                 mlp_dtype: str = "fp32") -> None:
+                 mlp_dtype: str = "fp32", sensor_layers: int = 1, sensor_dropout: float = 0.0) -> None:
         super().__init__()
         if mlp_dtype not in ("fp32", "bf16"):
             raise ValueError(f"mlp_dtype must be 'fp32' or 'bf16', got {mlp_dtype!r}")
@@ -128,7 +143,8 @@ class LeakDetector(nn.Module):
         self.sensor_node_ids = list(sensor_node_ids)
         self.sensor_node_idx = torch.tensor([self.node_to_idx[n] for n in self.sensor_node_ids], dtype=torch.long)
 
-        self.sensor_encoder = SharedSensorGRUEncoder(hidden_size=sensor_hidden, use_time=use_time)
+        self.sensor_encoder = SharedSensorGRUEncoder(hidden_size=sensor_hidden, num_layers=sensor_layers,
+                                                     dropout=sensor_dropout, use_time=use_time)
         self.sensor_to_node = nn.Linear(sensor_hidden + 1, node_hidden)
         self.convs = nn.ModuleList(
             [GCNConv(node_hidden, node_hidden, add_self_loops=True, normalize=True) for _ in range(gnn_layers)])

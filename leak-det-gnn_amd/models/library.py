@@ -12,6 +12,7 @@ ordinary ops (fake / meta implementations give output shapes without running ker
   leakgnn::mean_pool           PyG global_mean_pool over B equal windows (detector.py:215)
   leakgnn::sensor_proj         sensor_to_node on the sensor rows (detector.py:184-189)
   leakgnn::gru_encoder         SharedSensorGRUEncoder's GRU (detector.py:60-73)
+  leakgnn::gru_stack           the same with num_layers > 1 (dense-input upper layers, inter-layer dropout)
   leakgnn::gnn_trunk           node init + L x [GCNConv, ReLU, Dropout] (detector.py:178-201)
   leakgnn::detector_heads      pipe gather + EdgeHead + mean pool + NoLeakHead
                                (detector.py:76-102, 206-218)
@@ -482,6 +483,166 @@ def _gru_bwd(ctx, dh, _dhseq, _dgates):
 
 
 gru_encoder.register_autograd(_gru_bwd, setup_context=_gru_setup)
+
+
+# ============================================================================ gru_stack
+# nn.GRU(num_layers > 1) of the sensor encoder: layer 0 through lg_gru_fwd exactly as
+# gru_encoder runs it, every upper layer through lg_gru_seq_fwd on the h_seq the layer below
+# saved (no copy), inter-layer dropout applied on read (GRU_STACK_SALT + boundary).
+def _stack_dims(residual: Tensor, w_ih: List[Tensor], w_hh: List[Tensor]) -> Tuple[int, int, int, int, int, int]:
+    B, L, S = residual.shape
+    H = w_hh[0].shape[1]
+    nl = len(w_hh)
+    if nl < 1 or not (len(w_ih) == nl):
+        raise ValueError("gru_stack: one (w_ih, w_hh, b_ih, b_hh) per layer")
+    for l in range(nl):
+        want = (3 * H, w_ih[0].shape[1] if l == 0 else H)
+        if tuple(w_ih[l].shape) != want or tuple(w_hh[l].shape) != (3 * H, H):
+            raise ValueError(f"gru_stack: layer {l} weights {tuple(w_ih[l].shape)}, {tuple(w_hh[l].shape)}, "
+                             f"expected {want}, {(3 * H, H)}")
+    return B, L, S, w_ih[0].shape[1], H, nl
+
+
+@torch.library.custom_op(f"{NS}::gru_stack", mutates_args=(), device_types="cuda")
+def gru_stack(residual: Tensor, tfeat: Optional[Tensor], w_ih: List[Tensor], w_hh: List[Tensor], b_ih: List[Tensor],
+              b_hh: List[Tensor], p: float, seed: Tensor, save: bool) -> List[Tensor]:
+    """[h_L (B, S, H) of the top layer, h_seq_0 .. h_seq_{n-1}, gates_0 .. gates_{n-1}]: the stacked
+    GRU over the B*S sensor sequences.  p > 0: dropout between layers (train mode), mask of
+    boundary l (between layers l and l + 1) from (seed, GRU_STACK_SALT + l) over element index
+    (t * B*S + seq) * H + i.  save: keep every layer's gates for the backward (else they are
+    empty; the lower layers' h_seq are the upper layers' input either way)."""
+    from .ops import GRU_STACK_SALT
+    lib = load_library()
+    residual, tfeat = _c(residual), _c(tfeat)
+    w_ih, w_hh, b_ih, b_hh = ([_c(t) for t in ts] for ts in (w_ih, w_hh, b_ih, b_hh))
+    _req(residual, tfeat, *w_ih, *w_hh, *b_ih, *b_hh)
+    B, L, S, I, H, nl = _stack_dims(residual, w_ih, w_hh)
+    if tfeat is not None and tuple(tfeat.shape) != (B, L, 9):
+        raise ValueError(f"tfeat must be (B, L, 9), got {tuple(tfeat.shape)}")
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"gru_stack: dropout p must be in [0, 1), got {p}")
+    dev = residual.device
+    st = stream_of(residual)
+    nseq = B * S
+    drop = p > 0.0
+    seed_v, sbit = _seed_args(seed) if drop else (0, 0)
+    h_seqs = [torch.empty(L, nseq, H, device=dev) for _ in range(nl)]
+    gates = [torch.empty(L, nseq, 4, H, device=dev) if save else torch.empty(0, device=dev) for _ in range(nl)]
+    h_last = torch.empty(B, S, H, device=dev)
+    with _timed("gru_fwd", dev):
+        check(lib.lg_gru_fwd(ptr(residual), ptr(tfeat), ptr(w_ih[0]), ptr(w_hh[0]), ptr(b_ih[0]), ptr(b_hh[0]),
+                             ptr(h_seqs[0]), ptr(gates[0]) if save else None, ptr(h_last), B, L, S, I, H, st),
+              "lg_gru_fwd")
+    for l in range(1, nl):
+        with _timed("gru_seq_fwd", dev):
+            check(lib.lg_gru_seq_fwd(ptr(h_seqs[l - 1]), ptr(w_ih[l]), ptr(w_hh[l]), ptr(b_ih[l]), ptr(b_hh[l]),
+                                     ptr(h_seqs[l]), ptr(gates[l]) if save else None, nseq, L, H, H,
+                                     nat.LG_F_DROPOUT if drop else 0, p, seed_v, (GRU_STACK_SALT + l - 1) | sbit, st),
+                  "lg_gru_seq_fwd")
+    if nl > 1:  # lg_gru_fwd requires its h_last; the buffer is reused for the top layer's last step
+        h_last.copy_(h_seqs[-1][L - 1].view(B, S, H))
+    return [h_last] + h_seqs + gates
+
+
+@gru_stack.register_fake
+def _(residual, tfeat, w_ih, w_hh, b_ih, b_hh, p, seed, save):
+    B, L, S = residual.shape
+    H = w_hh[0].shape[1]
+    nl = len(w_hh)
+    return ([residual.new_empty(B, S, H)] + [residual.new_empty(L, B * S, H) for _ in range(nl)]
+            + [residual.new_empty(L, B * S, 4, H) if save else residual.new_empty(0) for _ in range(nl)])
+
+
+@torch.library.custom_op(f"{NS}::gru_stack_backward", mutates_args=(), device_types="cuda")
+def gru_stack_backward(dh: Tensor, residual: Tensor, tfeat: Optional[Tensor], w_ih: List[Tensor], w_hh: List[Tensor],
+                       h_seqs: List[Tensor], gates: List[Tensor], p: float, seed: Tensor, need_dx: bool
+                       ) -> List[Tensor]:
+    """[dx (B*S, L, I) or empty, dW_ih_0 .., dW_hh_0 .., db_ih_0 .., db_hh_0 ..]: BPTT down the stack
+    (lg_gru_seq_bwd).  The top layer takes dh (the gradient of h_L) alone, each layer's dx is the
+    layer below's per-step gradient, layer 0 reads (residual, tfeat) in place."""
+    from .ops import GRU_STACK_SALT
+    lib = load_library()
+    dh, residual, tfeat = _c(dh), _c(residual), _c(tfeat)
+    w_ih, w_hh = [_c(t) for t in w_ih], [_c(t) for t in w_hh]
+    _req(dh, residual, tfeat, *w_ih, *w_hh)
+    if any(g.numel() == 0 for g in gates):
+        raise RuntimeError("gru_stack was run with save=False; no backward")
+    B, L, S, I, H, nl = _stack_dims(residual, w_ih, w_hh)
+    dev = residual.device
+    st = stream_of(residual)
+    nseq = B * S
+    drop = p > 0.0
+    seed_v, sbit = _seed_args(seed) if drop else (0, 0)
+    dw_ih, dw_hh = [torch.empty_like(t) for t in w_ih], [torch.empty_like(t) for t in w_hh]
+    db_ih = [torch.empty(3 * H, device=dev) for _ in range(nl)]
+    db_hh = [torch.empty(3 * H, device=dev) for _ in range(nl)]
+    dx = torch.empty(nseq, L, I, device=dev) if need_dx else torch.empty(0, device=dev)
+    wss = [torch.empty(int(lib.lg_gru_seq_bwd_workspace_bytes(nseq, I if l == 0 else H, H)), device=dev,
+                       dtype=torch.uint8) for l in range(nl)]
+    dh_seq: Optional[Tensor] = None  # the layer above's dx
+    with _reduce_batch(lib, st), _timed("gru_bwd", dev):
+        for l in range(nl - 1, -1, -1):
+            top = l == nl - 1
+            if l > 0:
+                dxl = torch.empty(L, nseq, H, device=dev)
+                check(lib.lg_gru_seq_bwd(ptr(h_seqs[l - 1]), None, None, ptr(w_ih[l]), ptr(w_hh[l]), ptr(h_seqs[l]),
+                                         ptr(gates[l]), ptr(dh_seq), ptr(dh) if top else None, ptr(dxl), ptr(dw_ih[l]),
+                                         ptr(dw_hh[l]), ptr(db_ih[l]), ptr(db_hh[l]), 0, 0, nseq, L, H, H,
+                                         nat.LG_F_DROPOUT if drop else 0, p, seed_v, (GRU_STACK_SALT + l - 1) | sbit,
+                                         ptr(wss[l]), wss[l].numel(), st), "lg_gru_seq_bwd")
+                dh_seq = dxl
+            else:
+                check(lib.lg_gru_seq_bwd(None, ptr(residual), ptr(tfeat), ptr(w_ih[0]), ptr(w_hh[0]), ptr(h_seqs[0]),
+                                         ptr(gates[0]), ptr(dh_seq), ptr(dh) if top else None,
+                                         ptr(dx) if need_dx else None, ptr(dw_ih[0]), ptr(dw_hh[0]), ptr(db_ih[0]),
+                                         ptr(db_hh[0]), B, S, nseq, L, I, H, 0, 0.0, 0, 0, ptr(wss[0]),
+                                         wss[0].numel(), st), "lg_gru_seq_bwd")
+    return [dx] + dw_ih + dw_hh + db_ih + db_hh
+
+
+@gru_stack_backward.register_fake
+def _(dh, residual, tfeat, w_ih, w_hh, h_seqs, gates, p, seed, need_dx):
+    B, L, S = residual.shape
+    H = w_hh[0].shape[1]
+    dx = residual.new_empty(B * S, L, w_ih[0].shape[1]) if need_dx else residual.new_empty(0)
+    return ([dx] + [torch.empty_like(t) for t in w_ih] + [torch.empty_like(t) for t in w_hh]
+            + [residual.new_empty(3 * H) for _ in range(2 * len(w_hh))])
+
+
+def _gru_stack_setup(ctx, inputs, output):
+    residual, tfeat, w_ih, w_hh, _, _, p, seed, _ = inputs
+    nl = len(w_hh)
+    ctx.nl, ctx.p, ctx.has_tfeat = nl, p, tfeat is not None
+    ctx.mark_non_differentiable(*output[1:])
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(residual, tfeat if tfeat is not None else residual, seed, *w_ih, *w_hh, *output[1:])
+
+
+def _gru_stack_bwd(ctx, grads):
+    dh = grads[0]
+    if dh is None:
+        return (None,) * 9
+    nl = ctx.nl
+    sv = ctx.saved_tensors
+    residual, tfeat, seed = sv[:3]
+    w_ih, w_hh = list(sv[3:3 + nl]), list(sv[3 + nl:3 + 2 * nl])
+    h_seqs, gates = list(sv[3 + 2 * nl:3 + 3 * nl]), list(sv[3 + 3 * nl:])
+    B, L, S = residual.shape
+    I = w_ih[0].shape[1]
+    need_dx = ctx.needs_input_grad[0] or (ctx.has_tfeat and ctx.needs_input_grad[1])
+    out = torch.ops.leakgnn.gru_stack_backward(dh.contiguous(), residual, tfeat if ctx.has_tfeat else None, w_ih, w_hh,
+                                               h_seqs, gates, ctx.p, seed, need_dx)
+    dx = out[0]
+    dres = dtf = None
+    if ctx.needs_input_grad[0]:
+        dres = dx[..., 0].reshape(B, S, L).transpose(1, 2)
+    if ctx.has_tfeat and ctx.needs_input_grad[1]:
+        dtf = dx[..., 1:].reshape(B, S, L, I - 1).sum(dim=1)
+    g = out[1:]
+    return (dres, dtf, list(g[:nl]), list(g[nl:2 * nl]), list(g[2 * nl:3 * nl]), list(g[3 * nl:]), None, None, None)
+
+
+gru_stack.register_autograd(_gru_stack_bwd, setup_context=_gru_stack_setup)
 
 
 REDUCE_BATCH = True  # tests switch it off to compare with one reduction launch per op

@@ -300,6 +300,8 @@ def main():
                                                            "(LEAKGNN_LIB=lib/lab_stamps build only)")
     ap.add_argument("--probe", action="store_true", help="product-speed start/end timeline of each --nmlab train "
                                                           "launch of k_gcn_fwd_pc (LEAKGNN_LIB=lib/probe build only)")
+    ap.add_argument("--rounds", type=int, default=7, help="gru_stack leg: rounds of alternating windows")
+    ap.add_argument("--window-ms", type=float, default=250.0, help="gru_stack leg: device time per timed window")
     args = ap.parse_args()
     global GRAPH
     GRAPH = not args.eager
@@ -610,6 +612,86 @@ def main():
             res["gru_bwd"] = {"us": t, "TFLOPs": 2 * flops / t / 1e6}
             if args.stamps and hasattr(lib, "lg_lab_gru_stamps"):
                 res["stamps_gru_bwd"] = gru_stamps_summary(lib, f)
+    if "gru_stack" in which:
+        # the 2-layer sensor encoder (leakgnn::gru_stack) against (a) stock torch.nn.GRU(10, 64,
+        # num_layers=2) in fp32 on the same device, its (B*S, L, 10) input prebuilt, and (b) the
+        # one-layer HIP encoder; forward (no_grad) and forward + backward (weight gradients only).
+        # Module-level calls, so all three are timed the same way: eager launches between events,
+        # a synchronise at the end.  Each window runs for about --window-ms of device time
+        # (iterations from a calibration pass), the variants alternate within a round, and
+        # --rounds rounds give the median and the min .. max spread per figure.  The eager HIP
+        # figures include whatever host enqueue time the device does not hide, so the HIP
+        # forwards are also timed captured in one HIP graph (fwd_graph_us: device time alone).
+        from models.detector import SharedSensorGRUEncoder
+        S, L, H = 29, 36, 64
+        torch.manual_seed(0)
+        r, tf = torch.randn(B, L, S, device=dev), torch.randn(B, L, 9, device=dev)
+        xs = torch.cat([r.permute(0, 2, 1).reshape(B * S, L, 1),
+                        tf[:, None].expand(B, S, L, 9).reshape(B * S, L, 9)], dim=-1).contiguous()
+        enc1 = SharedSensorGRUEncoder(hidden_size=H).to(dev).eval()
+        enc2 = SharedSensorGRUEncoder(hidden_size=H, num_layers=2).to(dev).eval()
+        stock = torch.nn.GRU(10, H, num_layers=2, batch_first=True).to(dev)
+        stock.load_state_dict(enc2.gru.state_dict())
+        up = torch.randn(B, S, H, device=dev)
+
+        def window_us(fn, n):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(n):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) * 1e3 / n
+
+        def fwd(mod, stock_in):
+            def f():
+                with torch.no_grad():
+                    return mod(xs)[1][-1] if stock_in else mod(r, tf)
+            return f
+
+        def fwd_bwd(mod, stock_in):
+            ps = list(mod.parameters())
+
+            def f():
+                for p in ps:
+                    p.grad = None
+                out = mod(xs)[1][-1].view(B, S, H) if stock_in else mod(r, tf)
+                out.backward(up)
+            return f
+        mods = (("hip_2layer", enc2, False), ("torch_gru_2layer", stock, True), ("hip_1layer", enc1, False))
+        fns = {(name, k): mk(mod, si) for name, mod, si in mods for k, mk in (("fwd_us", fwd), ("fwd_bwd_us", fwd_bwd))}
+        iters = {}
+        for key, fn in fns.items():  # warm-up, then size the window from a short calibration
+            for _ in range(5):
+                fn()
+            torch.cuda.synchronize()
+            iters[key] = max(5, int(args.window_ms * 1e3 / window_us(fn, 5)))
+        samples = {key: [] for key in fns}
+        for _ in range(args.rounds):
+            for key, fn in fns.items():
+                samples[key].append(window_us(fn, iters[key]))
+        med = lambda v: float(np.median(v))
+        leg = {"rounds": args.rounds, "window_ms": args.window_ms}
+        for name, _, _ in mods:
+            leg[name] = {}
+            for k in ("fwd_us", "fwd_bwd_us"):
+                v = samples[(name, k)]
+                leg[name][k] = med(v)
+                leg[name][k[:-3] + "_min_max_us"] = [min(v), max(v)]
+                leg[name][k[:-3] + "_iters"] = iters[(name, k)]
+        for k in ("fwd_us", "fwd_bwd_us"):
+            # ratio per round (the variants of one round ran back to back), then median and spread
+            for other, tag in (("torch_gru_2layer", "torch"), ("hip_1layer", "1layer")):
+                q = [x / y for x, y in zip(samples[("hip_2layer", k)], samples[(other, k)])]
+                leg[f"{k[:-3]}_vs_{tag}"] = med(q)
+                leg[f"{k[:-3]}_vs_{tag}_min_max"] = [min(q), max(q)]
+        if GRAPH:
+            g = [[timeit(fns[(name, "fwd_us")], args.iters) for name in ("hip_2layer", "hip_1layer")] for _ in range(3)]
+            for i, name in enumerate(("hip_2layer", "hip_1layer")):
+                leg[name]["fwd_graph_us"] = med([row[i] for row in g])
+                leg[name]["fwd_graph_min_max_us"] = [min(row[i] for row in g), max(row[i] for row in g)]
+            leg["fwd_graph_vs_1layer"] = leg["hip_2layer"]["fwd_graph_us"] / leg["hip_1layer"]["fwd_graph_us"]
+        res["gru_stack"] = leg
     if "tcn" in which:
         # frozen-predictor residual builder, B segments of l_pred + l_det = 72 steps
         from models import tcn_plan
