@@ -728,8 +728,8 @@ int lg_gru_bwd(const float* residual, const float* tfeat, const float* w_ih, con
  *   the generic kernel's slab rows are capped by a 256 MiB budget).
  * H in {32, 64} with dense I == H: MFMA kernels (forward on the f16x2 split, the x scale taken
  * from the data per staging chunk; backward on fp32 MFMA).  H in {32, 64} in the encoder form:
- * lg_gru_bwd's fp32 MFMA kernel.  Any other H, I in 1..1024: generic kernels (one hidden unit
- * per thread).  LG_EUNSUPPORTED beyond 1024 or for other flags. */
+ * lg_gru_bwd's fp32 MFMA kernel.  H = 128, dense: the layers below (lg_gru_seq_tiled).  Any other
+ * H, I in 1..1024: generic kernels (one hidden unit per thread).  LG_EUNSUPPORTED beyond 1024 or for other flags. */
 int lg_gru_seq_fwd(const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
                    const float* b_hh, float* h_seq, float* gates,
                    int64_t Nseq, int64_t L, int64_t I, int64_t H,
@@ -742,6 +742,37 @@ int lg_gru_seq_bwd(const float* x, const float* residual, const float* tfeat,
                    int64_t B, int64_t S, int64_t Nseq, int64_t L, int64_t I, int64_t H,
                    int flags, float dropout_p, uint64_t seed, uint32_t salt,
                    void* workspace, int64_t ws_bytes, lg_stream_t stream);
+
+/* GRU layers at H = 128 (NormalPredictorGRU, reference models/predictor.py:84-111; added to ABI 26
+ * without a bump: additions only).
+ *   lg_gru_seq_tiled  1 where an MFMA kernel serves the dense form of lg_gru_seq_fwd (backward
+ *                     = 0) or lg_gru_seq_bwd (backward = 1), 0 where the generic kernel does: 1
+ *                     for (I, H) = (32, 32), (64, 64) and for H = 128 with any I in 1..1024.  The
+ *                     dispatchers use the same predicate.
+ * At H = 128 lg_gru_seq_fwd / lg_gru_seq_bwd run fp32-MFMA kernels (csrc/gru128.hip): the
+ * forward keeps W_hh (and W_ih for I <= 48) in registers, a wave owning all three gates of its 16
+ * units; the backward is a dh-chain recurrence that writes dG for a pass of steps into the
+ * workspace, followed by GEMM launches for dW_ih, dW_hh, the bias sums and dx, their row-block
+ * partials reduced in fixed order.  lg_gru_seq_bwd_workspace_bytes plans passes of up to 64 MiB
+ * of dG; a larger workspace makes the passes longer.
+ *   lg_gru_seq_infer  lg_gru_seq_fwd without gates, for H = 128 (LG_EUNSUPPORTED elsewhere):
+ *                     h_seq [L][Nseq][H] or NULL, h_last [Nseq][H] or NULL, at least one.  With
+ *                     h_seq == NULL nothing is written per step (the top layer of a stack whose
+ *                     reader wants h_L alone).
+ *   lg_gru_win_fwd    the shared-window form of a first layer (the residual builder, reference
+ *                     models/utils.py:169-216): gi fp32 [B][T][3H] holds W_ih x + b_ih per segment
+ *                     position, T >= l_pred + n_win - 1; sequence q = k * B + b (shift-major, the
+ *                     reference's row order, utils.py:194-212) reads gi[b][k + t] at step t, so
+ *                     the n_win windows of a segment are never unfolded.  h_seq [l_pred][n_win * B][H]
+ *                     or NULL, h_last [n_win * B][H] or NULL, at least one.  H = 128
+ *                     (LG_EUNSUPPORTED elsewhere).  Inference only. */
+int lg_gru_seq_tiled(int64_t I, int64_t H, int backward);
+int lg_gru_seq_infer(const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
+                     const float* b_hh, float* h_seq, float* h_last,
+                     int64_t Nseq, int64_t L, int64_t I, int64_t H,
+                     int flags, float dropout_p, uint64_t seed, uint32_t salt, lg_stream_t stream);
+int lg_gru_win_fwd(const float* gi, const float* w_hh, const float* b_hh, float* h_seq, float* h_last,
+                   int64_t B, int64_t T, int64_t l_pred, int64_t n_win, int64_t H, lg_stream_t stream);
 
 /* The GRU encoder and the node init in one launch each way (ABI 23; the node-major trunk's
  * compressed node init, lg_node_init_bits_fwd, with the sensor projection's backward,

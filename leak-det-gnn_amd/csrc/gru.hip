@@ -41,6 +41,7 @@
 #ifndef LG_GRU_LAUX
 #define LG_GRU_LAUX 0  // cache policy of the backward's h / gate loads (lab: 2 = nt)
 #endif
+#include "gru128.h"
 #include "reduce.h"
 #include "split_bf16.h"
 
@@ -2015,6 +2016,8 @@ inline int64_t seq_slab_len(int64_t I, int64_t H) { return 3 * H * (H + I) + 6 *
 inline bool seq_tiled(bool dense, int64_t I, int64_t H) {
     return (H == 32 || H == 64) && (dense ? I == H : (I == 1 || I == 10));
 }
+// H = 128: the gru128.hip layers, dense I in 1..1024, both directions (lg_gru_seq_tiled)
+inline bool seq_tiled128(bool dense, int64_t I, int64_t H) { return dense && H == kGru128H && I >= 1 && I <= 1024; }
 inline int64_t seq_bwd_rows(bool tiled, int64_t Nseq, int64_t I, int64_t H) {
     if (tiled) return std::max<int64_t>(1, nblocks_seq(Nseq));
     const int64_t fit = kSeqSlabBudget / (seq_slab_len(I, H) * static_cast<int64_t>(sizeof(float)));
@@ -2235,6 +2238,9 @@ extern "C" int lg_gru_seq_fwd(const float* x, const float* w_ih, const float* w_
     // the tiled kernel addresses one step's rows of its stores by 32-bit byte offsets: larger
     // calls run the generic kernel (64-bit offsets)
     const bool rows32 = Nseq * (gates ? 4 : 1) * H * 4 < (int64_t{1} << 31);
+    if (seq_tiled128(true, I, H))
+        return lg_gru128_fwd(x, w_ih, w_hh, b_ih, b_hh, h_seq, gates, nullptr, Nseq, L, I,
+                             LgGru128Drop{dr.on, dr.p, dr.scale, dr.seed, dr.salt}, s);
     if (seq_tiled(true, I, H) && rows32) {
         const unsigned grid = static_cast<unsigned>(nblocks_seq(Nseq));
         const uint32_t n = static_cast<uint32_t>(Nseq);
@@ -2256,6 +2262,7 @@ extern "C" int64_t lg_gru_seq_bwd_workspace_bytes(int64_t Nseq, int64_t I, int64
     if (Nseq < 0 || I < 1 || I > kGenMaxH || H < 1 || H > kGenMaxH) return LG_EINVAL;
     // I == H in {32, 64} can only be the dense tiled kernel; I in {1, 10} at those H is the tiled
     // encoder form or a dense generic call (the form is not known here): the larger of the two
+    if (seq_tiled128(true, I, H)) return lg_gru128_bwd_ws_bytes(Nseq, I);
     int64_t rows = seq_bwd_rows(seq_tiled(true, I, H), Nseq, I, H);
     if (seq_tiled(false, I, H)) rows = std::max(rows, seq_bwd_rows(true, Nseq, I, H));
     return rows * seq_slab_len(I, H) * static_cast<int64_t>(sizeof(float));
@@ -2277,6 +2284,11 @@ extern "C" int lg_gru_seq_bwd(const float* x, const float* residual, const float
     if (H > kGenMaxH || I > kGenMaxH) return LG_EUNSUPPORTED;
     if (!dense && ((I != 1 && I != 10) || (flags & LG_F_DROPOUT))) return LG_EUNSUPPORTED;  // the encoder's input is data
     if (!dense && I == 10 && !tfeat) return LG_EINVAL;
+    if (seq_tiled128(dense, I, H)) {
+        const SeqDrop d = seq_drop_args(flags, dropout_p, seed, salt);
+        return lg_gru128_bwd(x, w_ih, w_hh, h_seq, gates, dh_seq, dh_last, dx, dw_ih, dw_hh, db_ih, db_hh, Nseq, L, I,
+                             LgGru128Drop{d.on, d.p, d.scale, d.seed, d.salt}, workspace, ws_bytes, lg_stream(stream));
+    }
     const bool tiled = seq_tiled(dense, I, H);
     const int nb = static_cast<int>(seq_bwd_rows(tiled, Nseq, I, H));
     const int64_t len = seq_slab_len(I, H), G3 = 3 * H;
@@ -2321,4 +2333,34 @@ extern "C" int lg_gru_seq_bwd(const float* x, const float* residual, const float
     const LgSlabSeg segs[4] = {{0, nWhh, dw_hh}, {nWhh, nWih, dw_ih}, {nWhh + nWih, G3, db_ih},
                                {nWhh + nWih + G3, G3, db_hh}};
     return lg_launch_slab_reduce_multi(slab, nb, len, segs, 4, nullptr, nullptr, s);
+}
+
+extern "C" int lg_gru_seq_tiled(int64_t I, int64_t H, int backward) {
+    (void)backward;  // every tiled width has both directions
+    return (seq_tiled(true, I, H) || seq_tiled128(true, I, H)) ? 1 : 0;
+}
+
+extern "C" int lg_gru_seq_infer(const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
+                                const float* b_hh, float* h_seq, float* h_last, int64_t Nseq, int64_t L, int64_t I,
+                                int64_t H, int flags, float dropout_p, uint64_t seed, uint32_t salt,
+                                lg_stream_t stream) {
+    if (!seq_dims_ok(Nseq, L, I, H)) return LG_EINVAL;
+    if (!x || !w_ih || !w_hh || !b_ih || !b_hh || (!h_seq && !h_last)) return LG_EINVAL;
+    if ((flags & LG_F_DROPOUT) && !(dropout_p >= 0.f && dropout_p < 1.f)) return LG_EINVAL;
+    if (flags & ~LG_F_DROPOUT) return LG_EUNSUPPORTED;
+    if (!seq_tiled128(true, I, H)) return LG_EUNSUPPORTED;
+    if (Nseq == 0) return LG_OK;
+    const SeqDrop dr = seq_drop_args(flags, dropout_p, seed, salt);
+    return lg_gru128_fwd(x, w_ih, w_hh, b_ih, b_hh, h_seq, nullptr, h_last, Nseq, L, I,
+                         LgGru128Drop{dr.on, dr.p, dr.scale, dr.seed, dr.salt}, lg_stream(stream));
+}
+
+extern "C" int lg_gru_win_fwd(const float* gi, const float* w_hh, const float* b_hh, float* h_seq, float* h_last,
+                              int64_t B, int64_t T, int64_t l_pred, int64_t n_win, int64_t H, lg_stream_t stream) {
+    if (B < 0 || T <= 0 || l_pred <= 0 || n_win <= 0 || H <= 0 || l_pred > INT32_MAX) return LG_EINVAL;
+    if (T < l_pred + n_win - 1 || T >= (int64_t{1} << 31) || n_win * B >= (int64_t{1} << 31)) return LG_EINVAL;
+    if (!gi || !w_hh || !b_hh || (!h_seq && !h_last)) return LG_EINVAL;
+    if (H != kGru128H) return LG_EUNSUPPORTED;
+    if (B == 0) return LG_OK;
+    return lg_gru128_win_fwd(gi, w_hh, b_hh, h_seq, h_last, B, T, l_pred, n_win, lg_stream(stream));
 }

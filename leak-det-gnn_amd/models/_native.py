@@ -117,6 +117,9 @@ SIGNATURES = {
     # stacked GRU layers (added to ABI 26 without a bump: additions only)
     "lg_gru_seq_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _f32, _u64, _u32, _p]),
     "lg_gru_seq_bwd_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "lg_gru_seq_tiled": (_i32, [_i64, _i64, _i32]),
+    "lg_gru_seq_infer": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _f32, _u64, _u32, _p]),
+    "lg_gru_win_fwd": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p]),
     "lg_gru_seq_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64,
                               _i64, _i32, _f32, _u64, _u32, _p, _i64, _p]),
     "lg_gru_node_init_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,

@@ -13,6 +13,7 @@ ordinary ops (fake / meta implementations give output shapes without running ker
   leakgnn::sensor_proj         sensor_to_node on the sensor rows (detector.py:184-189)
   leakgnn::gru_encoder         SharedSensorGRUEncoder's GRU (detector.py:60-73)
   leakgnn::gru_stack           the same with num_layers > 1 (dense-input upper layers, inter-layer dropout)
+  leakgnn::gru_predictor       NormalPredictorGRU's nn.GRU over a dense (B, L, I) input (MFMA layers at H = 128)
   leakgnn::gnn_trunk           node init + L x [GCNConv, ReLU, Dropout] (detector.py:178-201)
   leakgnn::detector_heads      pipe gather + EdgeHead + mean pool + NoLeakHead
                                (detector.py:76-102, 206-218)
@@ -643,6 +644,180 @@ def _gru_stack_bwd(ctx, grads):
 
 
 gru_stack.register_autograd(_gru_stack_bwd, setup_context=_gru_stack_setup)
+
+
+# ============================================================================ gru_predictor
+# NormalPredictorGRU's nn.GRU (reference models/predictor.py:84-111) over a dense (B, L, I)
+# input: every layer through lg_gru_seq_fwd / lg_gru_seq_bwd (MFMA kernels at H = 128, the
+# generic kernels at other widths), the input copied once to time-major, inter-layer dropout
+# applied on read (GRU_PRED_SALT + boundary).
+def _predictor_dims(x: Tensor, w_ih: List[Tensor], w_hh: List[Tensor], b_ih: List[Tensor], b_hh: List[Tensor]
+                    ) -> Tuple[int, int, int, int, int]:
+    if x.dim() != 3:
+        raise ValueError(f"gru_predictor: x must be (B, L, I), got {tuple(x.shape)}")
+    B, L, I = x.shape
+    nl = len(w_hh)
+    if nl < 1 or not (len(w_ih) == len(b_ih) == len(b_hh) == nl):
+        raise ValueError("gru_predictor: one (w_ih, w_hh, b_ih, b_hh) per layer")
+    if w_hh[0].dim() != 2:
+        raise ValueError(f"gru_predictor: w_hh must be (3H, H), got {tuple(w_hh[0].shape)}")
+    H = w_hh[0].shape[1]
+    if L < 1 or not (1 <= I <= 1024 and 1 <= H <= 1024):
+        raise ValueError(f"gru_predictor: L >= 1 and I, H in 1..1024, got L {L}, I {I}, H {H}")
+    for l in range(nl):
+        want = (3 * H, I if l == 0 else H)
+        if (tuple(w_ih[l].shape) != want or tuple(w_hh[l].shape) != (3 * H, H) or tuple(b_ih[l].shape) != (3 * H,)
+                or tuple(b_hh[l].shape) != (3 * H,)):
+            raise ValueError(f"gru_predictor: layer {l} weights {tuple(w_ih[l].shape)}, {tuple(w_hh[l].shape)}, biases "
+                             f"{tuple(b_ih[l].shape)}, {tuple(b_hh[l].shape)}; expected {want}, {(3 * H, H)}, {(3 * H,)}")
+    return B, L, I, H, nl
+
+
+@torch.library.custom_op(f"{NS}::gru_predictor", mutates_args=(), device_types="cuda")
+def gru_predictor(x: Tensor, w_ih: List[Tensor], w_hh: List[Tensor], b_ih: List[Tensor], b_hh: List[Tensor],
+                  p: float, seed: Tensor, save: bool) -> List[Tensor]:
+    """[h_L (B, H) of the top layer, x time-major (L, B, I), h_seq_0 .. h_seq_{n-1}, gates_0 ..
+    gates_{n-1}].  p > 0: dropout between layers, mask of boundary l from (seed, GRU_PRED_SALT + l)
+    over element index (t * B + b) * H + i.  save=False (inference): no gates, and at H = 128 the
+    top layer writes h_L alone (lg_gru_seq_infer); the tensors not produced are empty."""
+    from .ops import GRU_PRED_SALT
+    lib = load_library()
+    x = _c(x)
+    w_ih, w_hh, b_ih, b_hh = ([_c(t) for t in ts] for ts in (w_ih, w_hh, b_ih, b_hh))
+    _req(x, *w_ih, *w_hh, *b_ih, *b_hh)
+    B, L, I, H, nl = _predictor_dims(x, w_ih, w_hh, b_ih, b_hh)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"gru_predictor: dropout p must be in [0, 1), got {p}")
+    dev = x.device
+    st = stream_of(x)
+    drop = p > 0.0
+    seed_v, sbit = _seed_args(seed) if drop else (0, 0)
+    xt = x.transpose(0, 1).clone(memory_format=torch.contiguous_format)  # never a view of x
+    h_last = torch.empty(B, H, device=dev)
+    h_seqs: List[Tensor] = []
+    gates: List[Tensor] = []
+    src = xt
+    for l in range(nl):
+        top = l == nl - 1
+        fl = nat.LG_F_DROPOUT if (drop and l > 0) else 0
+        salt = ((GRU_PRED_SALT + l - 1) | sbit) if fl else 0
+        Il = I if l == 0 else H
+        if top and not save and H == 128:
+            with _timed("gru_seq_infer", dev):
+                check(lib.lg_gru_seq_infer(ptr(src), ptr(w_ih[l]), ptr(w_hh[l]), ptr(b_ih[l]), ptr(b_hh[l]), None,
+                                           ptr(h_last), B, L, Il, H, fl, p if fl else 0.0, seed_v if fl else 0, salt, st),
+                      "lg_gru_seq_infer")
+            h_seqs.append(torch.empty(0, device=dev))
+            gates.append(torch.empty(0, device=dev))
+            continue
+        hs = torch.empty(L, B, H, device=dev)
+        g = torch.empty(L, B, 4, H, device=dev) if save else torch.empty(0, device=dev)
+        with _timed("gru_seq_fwd", dev):
+            check(lib.lg_gru_seq_fwd(ptr(src), ptr(w_ih[l]), ptr(w_hh[l]), ptr(b_ih[l]), ptr(b_hh[l]), ptr(hs),
+                                     ptr(g) if save else None, B, L, Il, H, fl, p if fl else 0.0, seed_v if fl else 0,
+                                     salt, st), "lg_gru_seq_fwd")
+        h_seqs.append(hs)
+        gates.append(g)
+        src = hs
+        if top:
+            h_last.copy_(hs[L - 1])
+    return [h_last, xt if save else torch.empty(0, device=dev)] + h_seqs + gates
+
+
+@gru_predictor.register_fake
+def _(x, w_ih, w_hh, b_ih, b_hh, p, seed, save):
+    B, L, I = x.shape
+    H = w_hh[0].shape[1]
+    nl = len(w_hh)
+    hs = [x.new_empty(L, B, H) for _ in range(nl)]
+    if not save and H == 128:
+        hs[-1] = x.new_empty(0)
+    return ([x.new_empty(B, H), x.new_empty(L, B, I) if save else x.new_empty(0)] + hs
+            + [x.new_empty(L, B, 4, H) if save else x.new_empty(0) for _ in range(nl)])
+
+
+@torch.library.custom_op(f"{NS}::gru_predictor_backward", mutates_args=(), device_types="cuda")
+def gru_predictor_backward(dh: Tensor, xt: Tensor, w_ih: List[Tensor], w_hh: List[Tensor], h_seqs: List[Tensor],
+                           gates: List[Tensor], p: float, seed: Tensor, need_dx: bool) -> List[Tensor]:
+    """[dx (B, L, I) or empty, dW_ih_0 .., dW_hh_0 .., db_ih_0 .., db_hh_0 ..]: BPTT down the stack
+    (lg_gru_seq_bwd).  Only the top layer takes dh (the gradient of h_L); each layer's dx is the
+    layer below's per-step gradient."""
+    from .ops import GRU_PRED_SALT
+    lib = load_library()
+    dh = _c(dh)
+    w_ih, w_hh = [_c(t) for t in w_ih], [_c(t) for t in w_hh]
+    _req(dh, xt, *w_ih, *w_hh)
+    if xt.numel() == 0 or any(g.numel() == 0 for g in gates):
+        raise RuntimeError("gru_predictor was run with save=False; no backward")
+    L, B, I = xt.shape
+    H = w_hh[0].shape[1]
+    nl = len(w_hh)
+    dev = xt.device
+    st = stream_of(xt)
+    drop = p > 0.0
+    seed_v, sbit = _seed_args(seed) if drop else (0, 0)
+    dw_ih, dw_hh = [torch.empty_like(t) for t in w_ih], [torch.empty_like(t) for t in w_hh]
+    db_ih = [torch.empty(3 * H, device=dev) for _ in range(nl)]
+    db_hh = [torch.empty(3 * H, device=dev) for _ in range(nl)]
+    dxt = torch.empty(L, B, I, device=dev) if need_dx else torch.empty(0, device=dev)
+    # the H = 128 backward takes its dG a pass of steps at a time: room for all L steps makes it one pass
+    extra = L * B * 4 * H * 4 if H == 128 else 0
+    wss = [torch.empty(int(lib.lg_gru_seq_bwd_workspace_bytes(B, I if l == 0 else H, H)) + extra, device=dev,
+                       dtype=torch.uint8) for l in range(nl)]
+    dh_seq: Optional[Tensor] = None
+    with _reduce_batch(lib, st), _timed("gru_seq_bwd", dev):
+        for l in range(nl - 1, -1, -1):
+            top = l == nl - 1
+            fl = nat.LG_F_DROPOUT if (drop and l > 0) else 0
+            salt = ((GRU_PRED_SALT + l - 1) | sbit) if fl else 0
+            src = xt if l == 0 else h_seqs[l - 1]
+            dxl = dxt if l == 0 else torch.empty(L, B, H, device=dev)
+            want_dx = l > 0 or need_dx
+            check(lib.lg_gru_seq_bwd(ptr(src), None, None, ptr(w_ih[l]), ptr(w_hh[l]), ptr(h_seqs[l]), ptr(gates[l]),
+                                     ptr(dh_seq), ptr(dh) if top else None, ptr(dxl) if want_dx else None,
+                                     ptr(dw_ih[l]), ptr(dw_hh[l]), ptr(db_ih[l]), ptr(db_hh[l]), 0, 0, B, L,
+                                     I if l == 0 else H, H, fl, p if fl else 0.0, seed_v if fl else 0, salt,
+                                     ptr(wss[l]), wss[l].numel(), st), "lg_gru_seq_bwd")
+            dh_seq = dxl
+    dx = dxt.transpose(0, 1).contiguous() if need_dx else dxt
+    return [dx] + dw_ih + dw_hh + db_ih + db_hh
+
+
+@gru_predictor_backward.register_fake
+def _(dh, xt, w_ih, w_hh, h_seqs, gates, p, seed, need_dx):
+    L, B, I = xt.shape
+    H = w_hh[0].shape[1]
+    dx = xt.new_empty(B, L, I) if need_dx else xt.new_empty(0)
+    return ([dx] + [torch.empty_like(t) for t in w_ih] + [torch.empty_like(t) for t in w_hh]
+            + [xt.new_empty(3 * H) for _ in range(2 * len(w_hh))])
+
+
+def _gru_predictor_setup(ctx, inputs, output):
+    _, w_ih, w_hh, _, _, p, seed, _ = inputs
+    ctx.nl, ctx.p = len(w_hh), p
+    ctx.mark_non_differentiable(*output[1:])
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(seed, *w_ih, *w_hh, *output[1:])
+
+
+def _gru_predictor_bwd(ctx, grads):
+    dh = grads[0]
+    if dh is None:
+        return (None,) * 8
+    nl = ctx.nl
+    sv = ctx.saved_tensors
+    seed = sv[0]
+    w_ih, w_hh = list(sv[1:1 + nl]), list(sv[1 + nl:1 + 2 * nl])
+    xt = sv[1 + 2 * nl]
+    h_seqs, gates = list(sv[2 + 2 * nl:2 + 3 * nl]), list(sv[2 + 3 * nl:])
+    need_dx = ctx.needs_input_grad[0]
+    out = torch.ops.leakgnn.gru_predictor_backward(dh.contiguous(), xt, w_ih, w_hh, h_seqs, gates, ctx.p, seed, need_dx)
+    g = out[1:]
+    return (out[0] if need_dx else None, list(g[:nl]), list(g[nl:2 * nl]), list(g[2 * nl:3 * nl]), list(g[3 * nl:]),
+            None, None, None)
+
+
+gru_predictor.register_autograd(_gru_predictor_bwd, setup_context=_gru_predictor_setup)
 
 
 REDUCE_BATCH = True  # tests switch it off to compare with one reduction launch per op

@@ -446,6 +446,7 @@ def _check_d(D: int) -> None:
 
 EDGE_HEAD_SALT = 101    # dropout stream of the EdgeHead hidden layer (trunk layers use salts 0..L)
 NOLEAK_HEAD_SALT = 102  # dropout stream of the NoLeakHead hidden layer
+GRU_PRED_SALT = 300     # + l: dropout between layers l and l + 1 of NormalPredictorGRU (library.gru_predictor)
 GRU_STACK_SALT = 200    # + l: dropout between layers l and l + 1 of a stacked sensor encoder (library.gru_stack)
 
 

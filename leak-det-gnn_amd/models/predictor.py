@@ -2,9 +2,12 @@
 
 Same constructors, forward signatures and state-dict keys as reference
 models/predictor.py (CausalConv1d :17-28, TCNBlock :31-52, NormalPredictorTCN
-:55-81, NormalPredictorGRU :84-111).  They contain no message passing and run on
-stock PyTorch-ROCm (MIOpen conv / GRU); SURVEY §8(f) ranks a fused TCN kernel as
-the next row after the GNN path.
+:55-81, NormalPredictorGRU :84-111).  They contain no message passing.  The TCN's training runs
+on stock PyTorch-ROCm (MIOpen conv); its frozen residual pass is models/tcn_plan.py.  On a ROCm
+GPU NormalPredictorGRU's nn.GRU runs on the library (leakgnn::gru_predictor: lg_gru_seq_fwd /
+lg_gru_seq_bwd, MFMA kernels at the default hidden_size 128, the generic kernels at other
+widths), forward and backward; its frozen residual pass is models/gru_plan.py.  On CPU tensors it
+is the stock module.
 """
 from __future__ import annotations
 
@@ -71,5 +74,15 @@ class NormalPredictorGRU(nn.Module):
         self.head = nn.Linear(hidden_size, self.num_sensors)
 
     def forward(self, x: torch.Tensor, x_time: torch.Tensor) -> torch.Tensor:
-        out, _ = self.gru(torch.cat([x, x_time], dim=-1))
+        xin = torch.cat([x, x_time], dim=-1)
+        g = self.gru
+        if xin.is_cuda and xin.dim() == 3 and g.batch_first and not g.bidirectional and g.bias and g.proj_size == 0:
+            from . import library
+            nl = g.num_layers
+            ws = [[getattr(g, f"{n}_l{l}") for l in range(nl)] for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+            p = float(g.dropout) if (self.training and nl > 1) else 0.0
+            save = torch.is_grad_enabled() and (xin.requires_grad or any(w.requires_grad for wl in ws for w in wl))
+            seed = library.seed_tensor(xin.device) if p > 0.0 else torch.zeros(1, dtype=torch.int64)
+            return self.head(torch.ops.leakgnn.gru_predictor(xin.float(), *ws, p, seed, save)[0])
+        out, _ = g(xin)
         return self.head(out[:, -1, :])

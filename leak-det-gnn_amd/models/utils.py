@@ -26,7 +26,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import tcn_plan
+from . import gru_plan, tcn_plan
 
 _SECTION = re.compile(r"^\s*\[(.+?)\]\s*$")
 
@@ -156,6 +156,11 @@ def build_residual_sequence_from_segment(predictor: Any, noisy_seg: Any, time_se
         # frozen default TCN on the GPU: one shared-window pass per segment (HIP,
         # lg_tcn_conv_fwd); same values as the per-window passes below within fp32 rounding
         res = tcn_plan.tcn_residual(predictor, noisy_seg.float(), time_seg.float(), l_pred, l_det)
+        return res.squeeze(0) if squeeze else res
+    if noisy_seg.is_cuda and RESIDUAL_FAST_PATH and gru_plan.fast_path_eligible(predictor):
+        # frozen NormalPredictorGRU (hidden 128) on the GPU: layer 0's input gates once per segment
+        # position, the windows read them in place (HIP, lg_gru_win_fwd / lg_gru_seq_infer)
+        res = gru_plan.gru_residual(predictor, noisy_seg.float(), time_seg.float(), l_pred, l_det).contiguous()
         return res.squeeze(0) if squeeze else res
     # (l_det, B, l_pred, C) windows via unfold: window k covers [k, k + l_pred)
     xw = noisy_seg.unfold(1, l_pred, 1)[:, :l_det].permute(1, 0, 3, 2).reshape(l_det * B, l_pred, S)

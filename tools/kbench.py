@@ -1,7 +1,7 @@
 """Kernel micro-benchmark (GPU): times individual libleakgnn kernels in isolation with
 HIP events on the launch stream.  Used for tuning and under rocprofv3 --pmc.
 
-  python tools/kbench.py [--which gcn_fwd,gcn_bwd,spmm,edge_fwd,edge_bwd,gru_fwd,gru_bwd] [--B 256] [--iters 50]
+  python tools/kbench.py [--which gcn_fwd,gcn_bwd,spmm,edge_fwd,edge_bwd,gru_fwd,gru_bwd,gru_stack,gru_predictor,tcn] [--B 256] [--iters 50]
 """
 import argparse
 import ctypes
@@ -692,6 +692,89 @@ def main():
                 leg[name]["fwd_graph_min_max_us"] = [min(row[i] for row in g), max(row[i] for row in g)]
             leg["fwd_graph_vs_1layer"] = leg["hip_2layer"]["fwd_graph_us"] / leg["hip_1layer"]["fwd_graph_us"]
         res["gru_stack"] = leg
+    if "gru_predictor" in which:
+        # NormalPredictorGRU (S = 29, hidden 128, 2 layers) at the residual builder's shape: B
+        # segments of l_pred + l_det = 72 steps, so l_det * B sequences of 36 steps, I = 38.
+        #   residual_fast   gru_plan.gru_residual (shared-window layer 0, lg_gru_seq_infer above)
+        #   residual_dense  leakgnn::gru_predictor on the unfolded windows (the module's route)
+        #   residual_stock  torch.nn.GRU (MIOpen) on the unfolded windows, the head, the subtraction
+        #   train_hip / train_stock   forward + backward of the module over (B, 36, 38), all gradients
+        #   dense_h128 / dense_h120   one lg_gru_seq_fwd layer, no gates, tiled (128) against generic (120)
+        # Same protocol as the gru_stack leg: windows of about --window-ms, the variants alternating
+        # within a round, --rounds rounds, median with min .. max.
+        import copy
+        from models import gru_plan
+        from models import utils as mutils
+        from models.predictor import NormalPredictorGRU
+        S, LP, LD = 29, 36, 36
+        torch.manual_seed(0)
+        m = NormalPredictorGRU(S, 9).eval().to(dev)
+        seg, tseg = torch.randn(B, LP + LD, S, device=dev), torch.randn(B, LP + LD, 9, device=dev)
+        stock_gru = copy.deepcopy(m.gru)
+
+        def stock_module(x, xt):
+            return m.head(stock_gru(torch.cat([x, xt], dim=-1))[0][:, -1])
+
+        def residual(fast, pred):
+            def f():
+                mutils.RESIDUAL_FAST_PATH = fast
+                try:
+                    with torch.no_grad():
+                        return mutils.build_residual_sequence_from_segment(pred, seg, tseg, LP, LD)
+                finally:
+                    mutils.RESIDUAL_FAST_PATH = True
+            return f
+        mt = copy.deepcopy(m).train()
+        mt.gru.dropout = 0.0  # both training legs without dropout: the same arithmetic
+        stock_t = copy.deepcopy(mt.gru)
+        xb, tb, up = torch.randn(B, LP, S, device=dev), torch.randn(B, LP, 9, device=dev), torch.randn(B, S, device=dev)
+
+        def train(hip):
+            ps = list(mt.parameters()) if hip else list(stock_t.parameters()) + list(mt.head.parameters())
+
+            def f():
+                for p in ps:
+                    p.grad = None
+                out = mt(xb, tb) if hip else mt.head(stock_t(torch.cat([xb, tb], dim=-1))[0][:, -1])
+                out.backward(up)
+            return f
+        nseq = LD * B
+
+        def dense(Hh):
+            g = torch.Generator(device="cpu").manual_seed(1)
+            ws = [torch.randn(3 * Hh, 38, generator=g).to(dev) * 0.1, torch.randn(3 * Hh, Hh, generator=g).to(dev) * 0.1,
+                  torch.zeros(3 * Hh, device=dev), torch.zeros(3 * Hh, device=dev)]
+            xd = torch.randn(LP, nseq, 38, device=dev)
+            hs = torch.empty(LP, nseq, Hh, device=dev)
+            return lambda: check(lib.lg_gru_seq_fwd(ptr(xd), *(ptr(w) for w in ws), ptr(hs), None, nseq, LP, 38, Hh, 0,
+                                                    0.0, 0, 0, cs()), "lg_gru_seq_fwd")
+        fns = {"residual_fast": residual(True, m), "residual_dense": residual(False, m),
+               "residual_stock": residual(False, stock_module), "train_hip": train(True), "train_stock": train(False),
+               "dense_h128": dense(128), "dense_h120": dense(120)}
+        assert gru_plan.fast_path_eligible(m)
+
+        def window_us(fn, n):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(n):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) * 1e3 / n
+        iters = {}
+        for key, fn in fns.items():
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            iters[key] = max(3, int(args.window_ms * 1e3 / window_us(fn, 3)))
+        samples = {key: [] for key in fns}
+        for _ in range(args.rounds):
+            for key, fn in fns.items():
+                samples[key].append(window_us(fn, iters[key]))
+        leg = {"rounds": args.rounds, "window_ms": args.window_ms, "B": B}
+        for key, v in samples.items():
+            leg[key] = {"us": float(np.median(v)), "min_max_us": [min(v), max(v)], "iters": iters[key]}
+        res["gru_predictor"] = leg
     if "tcn" in which:
         # frozen-predictor residual builder, B segments of l_pred + l_det = 72 steps
         from models import tcn_plan
