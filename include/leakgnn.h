@@ -820,6 +820,43 @@ int lg_tcn_conv_fwd(const float* in, const float* blk, const int32_t* plan, cons
                     int64_t nseg, int64_t rows_in, int64_t rows_blk, int64_t rows_out, int64_t C,
                     lg_stream_t stream);
 
+/* ---- NormalPredictorTCN training: one conv stage, forward and backward ----------------
+ * (Added to ABI 26 without a bump.)  The same table-driven rows as lg_tcn_conv_fwd; for
+ * training a segment is one sample, row t is time step t, and the table of dilation d is
+ * (t, t-d, t-2d, t or -1).  C = 128, rows_out <= 2048 and every tensor of a call below 2 GiB
+ * (LG_EUNSUPPORTED otherwise; the training calls do not split into several launches).
+ *   lg_tcn_conv_train_fwd  s = dropout_p(relu(LayerNorm(conv(x) + bias))), out = s + residual.
+ *       Keep mask: the library's counter RNG under key(seed, salt) at element index
+ *       global_row * 128 + channel, global_row over [nseg * rows_out]; LG_SALT_SEED_PTR honoured.  s (the stage output before the residual
+ *       add) is always stored; out is required with blk and optional without (then out = s).
+ *       xhat [nseg*rows_out][C] (normalised conv output) and rstd [nseg*rows_out] are what the
+ *       backward reads; both or neither.  p = 0 without xhat / rstd is lg_tcn_conv_fwd's launch
+ *       (result in out, or in s when there is no blk and s is given).
+ *   lg_tcn_pack_weight_t   Conv1d weight -> packed fragment order of the backward's dx GEMM
+ *       (co and ci exchanged).
+ *   lg_tcn_conv_bwd        from dy (gradient of out) and the saved s, xhat, rstd:
+ *       dz [nseg*rows_out][C] (gradient of the conv output), dw [C][C][3], db, dgamma, dbeta
+ *       (all overwritten), and, unless dx is NULL, dx [nseg*rows_in][C] =
+ *       sum_j dz[plan_t[t][j]] W_j^T + dres[plan_t[t].w]: plan_t is the transposed table
+ *       (t, t+d, t+2d, row of dres or -1; -1 where no output row reads the tap), dres
+ *       ([nseg][rows_res][C], may be NULL) the gradient that bypasses the stage (conv1: the
+ *       block output's).  in is the stage's forward input, plan its forward table.  Row sums go
+ *       through per-workgroup partials in the workspace and the fixed-order slab reduction: no
+ *       atomics, equal results on every run.  ws_bytes below
+ *       lg_tcn_conv_bwd_workspace_bytes(nseg, rows_out, C) is LG_EINVAL. */
+int lg_tcn_pack_weight_t(const float* weight, float* packed, int64_t C, lg_stream_t stream);
+int lg_tcn_conv_train_fwd(const float* in, const float* blk, const int32_t* plan, const float* packed_weight,
+                          const float* bias, const float* ln_w, const float* ln_b, float eps, float p,
+                          uint64_t seed, uint32_t salt, float* s, float* out, float* xhat, float* rstd,
+                          int64_t nseg, int64_t rows_in, int64_t rows_blk, int64_t rows_out, int64_t C,
+                          lg_stream_t stream);
+int64_t lg_tcn_conv_bwd_workspace_bytes(int64_t nseg, int64_t rows_out, int64_t C);
+int lg_tcn_conv_bwd(const float* dy, const float* s, const float* xhat, const float* rstd, const float* in,
+                    const float* dres, const int32_t* plan, const int32_t* plan_t, const float* packed_weight_t,
+                    const float* ln_w, float p, float* dz, float* dx, float* dw, float* db, float* dgamma,
+                    float* dbeta, int64_t nseg, int64_t rows_in, int64_t rows_res, int64_t rows_out, int64_t C,
+                    void* workspace, int64_t ws_bytes, lg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

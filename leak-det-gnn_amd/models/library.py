@@ -14,6 +14,7 @@ ordinary ops (fake / meta implementations give output shapes without running ker
   leakgnn::gru_encoder         SharedSensorGRUEncoder's GRU (detector.py:60-73)
   leakgnn::gru_stack           the same with num_layers > 1 (dense-input upper layers, inter-layer dropout)
   leakgnn::gru_predictor       NormalPredictorGRU's nn.GRU over a dense (B, L, I) input (MFMA layers at H = 128)
+  leakgnn::tcn_predictor       NormalPredictorTCN's conv stack over the projected (B, L, 128) input, for training
   leakgnn::gnn_trunk           node init + L x [GCNConv, ReLU, Dropout] (detector.py:178-201)
   leakgnn::detector_heads      pipe gather + EdgeHead + mean pool + NoLeakHead
                                (detector.py:76-102, 206-218)
@@ -30,6 +31,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 
+from collections import OrderedDict
 from typing import List, Optional, Tuple
 
 import torch
@@ -818,6 +820,207 @@ def _gru_predictor_bwd(ctx, grads):
 
 
 gru_predictor.register_autograd(_gru_predictor_bwd, setup_context=_gru_predictor_setup)
+
+
+# ============================================================================ tcn_predictor
+# NormalPredictorTCN's conv stack (reference models/predictor.py:31-81) over the output of the input
+# projection: every [conv -> LayerNorm -> ReLU -> Dropout] stage is one lg_tcn_conv_train_fwd launch
+# (the residual add fused into conv2) and one lg_tcn_conv_bwd call (elementwise / LayerNorm backward,
+# dx as the conv kernel over the transposed table, dW as an MFMA GEMM over all rows).  Dropout mask of
+# conv i: (seed, TCN_SALT + i) over element index (b * L + t) * 128 + c.
+_TCN_PACK_CACHE: "OrderedDict[int, tuple]" = OrderedDict()
+_TCN_PACK_MAX = 64
+
+
+def _tcn_packed(w: Tensor) -> Tuple[Tensor, Tensor]:
+    """(packed, transposed-packed) forms of a Conv1d weight (lg_tcn_pack_weight / _t), cached per
+    parameter (data_ptr, _version) as tcn_plan._packed_weights does: an in-place optimizer step bumps
+    the version and so invalidates the entry.  An entry keeps its weight tensor alive, so its address
+    cannot be handed to another tensor while the entry exists; the oldest entries are dropped."""
+    lib = load_library()
+    try:
+        stamp = (w.data_ptr(), w._version)
+    except RuntimeError:  # an inference tensor has no version counter: not cached
+        stamp = None
+    if stamp is not None:
+        hit = _TCN_PACK_CACHE.get(stamp[0])
+        if hit is not None and hit[0] == stamp[1]:
+            _TCN_PACK_CACHE.move_to_end(stamp[0])
+            return hit[2], hit[3]
+    n = int(lib.lg_tcn_packed_weight_floats(128))
+    pk, pkt = torch.empty(n, device=w.device), torch.empty(n, device=w.device)
+    st = stream_of(w)
+    check(lib.lg_tcn_pack_weight(ptr(w), ptr(pk), 128, st), "lg_tcn_pack_weight")
+    check(lib.lg_tcn_pack_weight_t(ptr(w), ptr(pkt), 128, st), "lg_tcn_pack_weight_t")
+    if stamp is not None:
+        _TCN_PACK_CACHE[stamp[0]] = (stamp[1], w, pk, pkt)
+        _TCN_PACK_CACHE.move_to_end(stamp[0])
+        while len(_TCN_PACK_CACHE) > _TCN_PACK_MAX:
+            _TCN_PACK_CACHE.popitem(last=False)
+    return pk, pkt
+
+
+def _tcn_dims(x: Tensor, conv_w: List[Tensor], conv_b: List[Tensor], ln_w: List[Tensor], ln_b: List[Tensor]
+              ) -> Tuple[int, int, int]:
+    if x.dim() != 3 or x.shape[2] != 128:
+        raise ValueError(f"tcn_predictor: x must be (B, L, 128), got {tuple(x.shape)}")
+    B, L, C = x.shape
+    n = len(conv_w)
+    if n < 2 or n % 2 or not (len(conv_b) == len(ln_w) == len(ln_b) == n):
+        raise ValueError("tcn_predictor: two (conv weight, conv bias, LayerNorm weight, LayerNorm bias) per block")
+    if not 1 <= L <= 2048:
+        raise ValueError(f"tcn_predictor: L must be in 1..2048, got {L}")
+    if B * L * C * 4 >= 2 ** 31:
+        raise ValueError(f"tcn_predictor: B * L * 512 bytes must stay below 2 GiB, got B {B}, L {L}")
+    for i in range(n):
+        if tuple(conv_w[i].shape) != (C, C, 3) or any(tuple(t[i].shape) != (C,) for t in (conv_b, ln_w, ln_b)):
+            raise ValueError(f"tcn_predictor: conv {i} needs a (128, 128, 3) weight and (128,) bias / LayerNorm "
+                             f"vectors, got {tuple(conv_w[i].shape)}")
+    return B, L, n
+
+
+@torch.library.custom_op(f"{NS}::tcn_predictor", mutates_args=(), device_types="cuda")
+def tcn_predictor(x: Tensor, conv_w: List[Tensor], conv_b: List[Tensor], ln_w: List[Tensor], ln_b: List[Tensor],
+                  eps: float, p: float, seed: Tensor, save: bool) -> List[Tensor]:
+    """[h_last (B, 128) = the last block's output at t = L - 1, s_0 .. s_{n-1}, xhat_0 .., rstd_0 ..,
+    block outputs 0 .. n/2 - 1] for x (B, L, 128), the input projection's output, and n = 2 * blocks
+    conv stages with dilation 2 ** (i // 2).  s_i (B * L, 128) is stage i's output before the residual
+    add, xhat_i / rstd_i its normalised conv output and 1 / sqrt(var + eps) (the LayerNorm backward's
+    inputs).  save=False (no backward): only h_last, the other tensors are empty."""
+    from .ops import TCN_SALT
+    from .tcn_plan import train_tables
+    lib = load_library()
+    x = _c(x)
+    conv_w, conv_b, ln_w, ln_b = ([_c(t) for t in ts] for ts in (conv_w, conv_b, ln_w, ln_b))
+    _req(x, *conv_w, *conv_b, *ln_w, *ln_b)
+    B, L, n = _tcn_dims(x, conv_w, conv_b, ln_w, ln_b)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"tcn_predictor: dropout p must be in [0, 1), got {p}")
+    C = 128
+    dev = x.device
+    st = stream_of(x)
+    seed_v, sbit = _seed_args(seed) if p > 0.0 else (0, 0)
+    tabs, _ = train_tables(L, [2 ** b for b in range(n // 2)], dev)
+    none = torch.empty(0, device=dev)
+    ss, xhs, rss, outs = [], [], [], []
+    blk_in = x.view(B * L, C)
+    src = blk_in
+    with _timed("tcn_train_fwd", dev):
+        for i in range(n):
+            conv2 = i % 2 == 1
+            pk, _ = _tcn_packed(conv_w[i])
+            s = torch.empty(B * L, C, device=dev) if (save or p > 0.0 or not conv2) else None
+            out = torch.empty(B * L, C, device=dev) if conv2 else None
+            xh = torch.empty(B * L, C, device=dev) if save else None
+            rs = torch.empty(B * L, device=dev) if save else None
+            check(lib.lg_tcn_conv_train_fwd(ptr(src), ptr(blk_in) if conv2 else None, ptr(tabs[i]), ptr(pk),
+                                            ptr(conv_b[i]), ptr(ln_w[i]), ptr(ln_b[i]), eps, p, seed_v,
+                                            ((TCN_SALT + i) | sbit) if p > 0.0 else 0, ptr(s), ptr(out), ptr(xh),
+                                            ptr(rs), B, L, L if conv2 else 0, L, C, st), "lg_tcn_conv_train_fwd")
+            if save:
+                ss.append(s)
+                xhs.append(xh)
+                rss.append(rs)
+            if conv2:
+                if save:
+                    outs.append(out)
+                blk_in = src = out
+            else:
+                src = s
+    h_last = blk_in.view(B, L, C)[:, L - 1].clone(memory_format=torch.contiguous_format)
+    if not save:
+        return [h_last] + [none.clone() for _ in range(3 * n + n // 2)]
+    return [h_last] + ss + xhs + rss + outs
+
+
+@tcn_predictor.register_fake
+def _(x, conv_w, conv_b, ln_w, ln_b, eps, p, seed, save):
+    B, L, C = x.shape
+    n = len(conv_w)
+    if not save:
+        return [x.new_empty(B, C)] + [x.new_empty(0) for _ in range(3 * n + n // 2)]
+    return ([x.new_empty(B, C)] + [x.new_empty(B * L, C) for _ in range(2 * n)] + [x.new_empty(B * L) for _ in range(n)]
+            + [x.new_empty(B * L, C) for _ in range(n // 2)])
+
+
+@torch.library.custom_op(f"{NS}::tcn_predictor_backward", mutates_args=(), device_types="cuda")
+def tcn_predictor_backward(dh: Tensor, x: Tensor, conv_w: List[Tensor], ln_w: List[Tensor], s: List[Tensor],
+                           xhat: List[Tensor], rstd: List[Tensor], outs: List[Tensor], p: float,
+                           need_dx: bool) -> List[Tensor]:
+    """[dx (B, L, 128) or empty, dW_0 .., db_0 .., dgamma_0 .., dbeta_0 ..] for dh, the gradient of
+    h_last: lg_tcn_conv_bwd down the stages.  Every gradient is overwritten, none accumulated into."""
+    from .tcn_plan import train_tables
+    lib = load_library()
+    dh, x = _c(dh), _c(x)
+    conv_w, ln_w = [_c(t) for t in conv_w], [_c(t) for t in ln_w]
+    _req(dh, x, *conv_w, *ln_w)
+    n = len(conv_w)
+    if len(s) != n or any(t.numel() == 0 for t in s):
+        raise RuntimeError("tcn_predictor was run with save=False; no backward")
+    B, L, C = x.shape
+    dev = x.device
+    st = stream_of(x)
+    tabs, tabs_t = train_tables(L, [2 ** b for b in range(n // 2)], dev)
+    dws = [torch.empty(C, C, 3, device=dev) for _ in range(n)]
+    dbs, dgs, dbts = ([torch.empty(C, device=dev) for _ in range(n)] for _ in range(3))
+    ws = torch.empty(int(lib.lg_tcn_conv_bwd_workspace_bytes(B, L, C)), device=dev, dtype=torch.uint8)
+    dz = torch.empty(B * L, C, device=dev)
+    dy = torch.zeros(B, L, C, device=dev)
+    dy[:, L - 1] = dh
+    dy = dy.view(B * L, C)
+
+    def stage(i, dy_i, src, dres, dx):
+        _, pkt = _tcn_packed(conv_w[i])
+        check(lib.lg_tcn_conv_bwd(ptr(dy_i), ptr(s[i]), ptr(xhat[i]), ptr(rstd[i]), ptr(src), ptr(dres), ptr(tabs[i]),
+                                  ptr(tabs_t[i]), ptr(pkt), ptr(ln_w[i]), p, ptr(dz), ptr(dx), ptr(dws[i]), ptr(dbs[i]),
+                                  ptr(dgs[i]), ptr(dbts[i]), B, L, L if dres is not None else 0, L, C, ptr(ws),
+                                  ws.numel(), st), "lg_tcn_conv_bwd")
+
+    with _timed("tcn_train_bwd", dev):
+        for b in range(n // 2 - 1, -1, -1):
+            blk_in = x.view(B * L, C) if b == 0 else outs[b - 1]
+            ds1 = torch.empty(B * L, C, device=dev)
+            stage(2 * b + 1, dy, s[2 * b], None, ds1)            # conv2: its input is conv1's output
+            want_dx = b > 0 or need_dx
+            dprev = torch.empty(B * L, C, device=dev) if want_dx else None
+            stage(2 * b, ds1, blk_in, dy if want_dx else None, dprev)  # conv1: + the residual's pass-through
+            dy = dprev
+    dx = dy.view(B, L, C) if need_dx else torch.empty(0, device=dev)
+    return [dx] + dws + dbs + dgs + dbts
+
+
+@tcn_predictor_backward.register_fake
+def _(dh, x, conv_w, ln_w, s, xhat, rstd, outs, p, need_dx):
+    n = len(conv_w)
+    return ([torch.empty_like(x) if need_dx else x.new_empty(0)] + [torch.empty_like(t) for t in conv_w]
+            + [x.new_empty(128) for _ in range(3 * n)])
+
+
+def _tcn_predictor_setup(ctx, inputs, output):
+    x, conv_w, _, ln_w, _, _, p, _, _ = inputs
+    ctx.n, ctx.p = len(conv_w), p
+    ctx.mark_non_differentiable(*output[1:])
+    ctx.set_materialize_grads(False)
+    ctx.save_for_backward(x, *conv_w, *ln_w, *output[1:])
+
+
+def _tcn_predictor_bwd(ctx, grads):
+    dh = grads[0]
+    if dh is None:
+        return (None,) * 9
+    n = ctx.n
+    sv = ctx.saved_tensors
+    x, conv_w, ln_w = sv[0], list(sv[1:1 + n]), list(sv[1 + n:1 + 2 * n])
+    rest = sv[1 + 2 * n:]
+    s, xhat, rstd, outs = list(rest[:n]), list(rest[n:2 * n]), list(rest[2 * n:3 * n]), list(rest[3 * n:])
+    need_dx = ctx.needs_input_grad[0]
+    out = torch.ops.leakgnn.tcn_predictor_backward(dh.contiguous(), x, conv_w, ln_w, s, xhat, rstd, outs, ctx.p, need_dx)
+    g = out[1:]
+    return (out[0] if need_dx else None, list(g[:n]), list(g[n:2 * n]), list(g[2 * n:3 * n]), list(g[3 * n:]),
+            None, None, None, None)
+
+
+tcn_predictor.register_autograd(_tcn_predictor_bwd, setup_context=_tcn_predictor_setup)
 
 
 REDUCE_BATCH = True  # tests switch it off to compare with one reduction launch per op

@@ -448,6 +448,7 @@ EDGE_HEAD_SALT = 101    # dropout stream of the EdgeHead hidden layer (trunk lay
 NOLEAK_HEAD_SALT = 102  # dropout stream of the NoLeakHead hidden layer
 GRU_PRED_SALT = 300     # + l: dropout between layers l and l + 1 of NormalPredictorGRU (library.gru_predictor)
 GRU_STACK_SALT = 200    # + l: dropout between layers l and l + 1 of a stacked sensor encoder (library.gru_stack)
+TCN_SALT = 400          # + conv index 0..7: dropout of NormalPredictorTCN's stages (library.tcn_predictor)
 
 
 def pipe_features(h: torch.Tensor, inc: Incidence) -> torch.Tensor:

@@ -252,3 +252,41 @@ def tcn_residual(predictor, noisy_seg, time_seg, l_pred: int, l_det: int):
         final = last.view(B, rows_last, C).index_select(1, dp.out_rows)                 # (B, l_det, C)
         y_hat = torch.addmm(predictor.head.bias, final.reshape(B * l_det, C), predictor.head.weight.t())
         return noisy_seg[:, l_pred:, :] - y_hat.view(B, l_det, S)
+
+
+# --------------------------------------------------------------------------------------
+# Training tables (library.tcn_predictor): a segment is one sample, row t is time step t.
+# --------------------------------------------------------------------------------------
+_TRAIN_TABLES: Dict[Tuple[int, Tuple[int, ...], str], tuple] = {}
+
+
+def train_tables(L: int, dilations: Sequence[int], device=None):
+    """(forward tables, transposed tables) of a TCN's conv stages over L time steps, two stages
+    (conv1, conv2) per dilation, each an (L, 4) int32 array in lg_tcn_conv_fwd's table form.
+      forward    (t, t - d, t - 2d, res): res = t for conv2 (the block input row), -1 for conv1;
+      transposed (t, t + d, t + 2d, res): the output rows that read row t through tap 0, 1, 2
+                 (the backward's dx gathers dz through it); res = t for conv1, whose input is the
+                 block input and so also receives the block output's gradient, -1 for conv2.
+    -1 where the row does not exist.  numpy arrays when device is None, else int32 tensors on
+    that device; cached per (L, dilations, device)."""
+    key = (int(L), tuple(int(d) for d in dilations), str(device))
+    hit = _TRAIN_TABLES.get(key)
+    if hit is not None:
+        return hit
+    if L < 1:
+        raise ValueError(f"train_tables: L must be >= 1, got {L}")
+    t = np.arange(L, dtype=np.int64)
+    none = np.full(L, -1, dtype=np.int64)
+    fwd, tr = [], []
+    for d in key[1]:
+        back = [np.where(t - j * d >= 0, t - j * d, -1) for j in range(3)]
+        ahead = [np.where(t + j * d < L, t + j * d, -1) for j in range(3)]
+        for conv2 in (False, True):
+            fwd.append(np.ascontiguousarray(np.stack(back + [t if conv2 else none], 1).astype(np.int32)))
+            tr.append(np.ascontiguousarray(np.stack(ahead + [none if conv2 else t], 1).astype(np.int32)))
+    if device is not None:
+        import torch
+        fwd = [torch.from_numpy(a).to(device) for a in fwd]
+        tr = [torch.from_numpy(a).to(device) for a in tr]
+    _TRAIN_TABLES[key] = (fwd, tr)
+    return fwd, tr

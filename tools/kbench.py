@@ -1,7 +1,7 @@
 """Kernel micro-benchmark (GPU): times individual libleakgnn kernels in isolation with
 HIP events on the launch stream.  Used for tuning and under rocprofv3 --pmc.
 
-  python tools/kbench.py [--which gcn_fwd,gcn_bwd,spmm,edge_fwd,edge_bwd,gru_fwd,gru_bwd,gru_stack,gru_predictor,tcn] [--B 256] [--iters 50]
+  python tools/kbench.py [--which gcn_fwd,gcn_bwd,spmm,edge_fwd,edge_bwd,gru_fwd,gru_bwd,gru_stack,gru_predictor,tcn,tcn_train] [--B 256] [--iters 50]
 """
 import argparse
 import ctypes
@@ -811,6 +811,86 @@ def main():
             t = timeit(f, max(3, args.iters // 10))
             res["tcn_residual_stock"] = {"us": t, "segments_per_s": B / t * 1e6}
             mutils.RESIDUAL_FAST_PATH = True
+    if "tcn_train" in which:
+        # NormalPredictorTCN training step at train_predictor's shape: (B, 36, 38), train mode, p = 0.1,
+        # forward + backward of the module with all gradients.
+        #   train_hip    leakgnn::tcn_predictor (lg_tcn_conv_train_fwd / lg_tcn_conv_bwd)
+        #   train_stock  the same module and weights on the stock route (MIOpen conv, LayerNorm, ReLU, Dropout)
+        # gru_stack's protocol: windows of about --window-ms, the variants alternating within a round,
+        # --rounds rounds, median with min .. max.  Then one stage alone (every stage has B * 36 rows).
+        from models import predictor as mpred
+        from models.ops import TCN_SALT
+        from models.tcn_plan import train_tables
+        S, L = 29, 36
+        torch.manual_seed(0)
+        mt = mpred.NormalPredictorTCN(S, 9).train().to(dev)
+        xb, tb, up = torch.randn(B, L, S, device=dev), torch.randn(B, L, 9, device=dev), torch.randn(B, S, device=dev)
+        ps = list(mt.parameters())
+
+        def train(hip):
+            def f():
+                mpred.TCN_TRAIN_HIP = hip
+                try:
+                    for p in ps:
+                        p.grad = None
+                    mt(xb, tb).backward(up)
+                finally:
+                    mpred.TCN_TRAIN_HIP = True
+            return f
+        fns = {"train_hip": train(True), "train_stock": train(False)}
+
+        def window_us(fn, n):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(n):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) * 1e3 / n
+        iters = {}
+        for key, fn in fns.items():
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            iters[key] = max(3, int(args.window_ms * 1e3 / window_us(fn, 3)))
+        samples = {key: [] for key in fns}
+        for _ in range(args.rounds):
+            for key, fn in fns.items():
+                samples[key].append(window_us(fn, iters[key]))
+        leg = {"rounds": args.rounds, "window_ms": args.window_ms, "B": B}
+        for key, v in samples.items():
+            leg[key] = {"us": float(np.median(v)), "min_max_us": [min(v), max(v)], "iters": iters[key]}
+        leg["hip_slowest_beats_stock_fastest"] = max(samples["train_hip"]) < min(samples["train_stock"])
+        res["tcn_train"] = leg
+        # one stage (conv2 form, d = 8): training forward, backward, backward without dx
+        R, C = B * L, 128
+        fwd_t, tr_t = train_tables(L, (1, 2, 4, 8), dev)
+        blk = mt.tcn[3]
+        n = lib.lg_tcn_packed_weight_floats(C)
+        pk, pkt = torch.empty(n, device=dev), torch.empty(n, device=dev)
+        check(lib.lg_tcn_pack_weight(ptr(blk.conv2.conv.weight), ptr(pk), C, cs()), "pack")
+        check(lib.lg_tcn_pack_weight_t(ptr(blk.conv2.conv.weight), ptr(pkt), C, cs()), "pack_t")
+        xin, bin_, dy = (torch.randn(R, C, device=dev) for _ in range(3))
+        s, out, xh, dz, dx = (torch.empty(R, C, device=dev) for _ in range(5))
+        rs = torch.empty(R, device=dev)
+        dw, db, dg, dbt = torch.empty(C, C, 3, device=dev), *(torch.empty(C, device=dev) for _ in range(3))
+        ws = torch.empty(int(lib.lg_tcn_conv_bwd_workspace_bytes(B, L, C)), dtype=torch.uint8, device=dev)
+        f = lambda: check(lib.lg_tcn_conv_train_fwd(ptr(xin), ptr(bin_), ptr(fwd_t[7]), ptr(pk), ptr(blk.conv2.conv.bias),
+                                                    ptr(blk.norm2.weight), ptr(blk.norm2.bias), 1e-5, 0.1, 123,
+                                                    TCN_SALT + 7, ptr(s), ptr(out), ptr(xh), ptr(rs), B, L, L, L, C, cs()),
+                          "train fwd")
+        t = timeit(f, args.iters)
+        res["tcn_stage_fwd"] = {"us": t, "TFLOPs": R * 2 * 128 * 384 / t / 1e6}
+
+        def bwd(with_dx):
+            return lambda: check(lib.lg_tcn_conv_bwd(ptr(dy), ptr(s), ptr(xh), ptr(rs), ptr(xin), None, ptr(fwd_t[7]),
+                                                     ptr(tr_t[7]) if with_dx else None, ptr(pkt) if with_dx else None,
+                                                     ptr(blk.norm2.weight), 0.1, ptr(dz), ptr(dx) if with_dx else None,
+                                                     ptr(dw), ptr(db), ptr(dg), ptr(dbt), B, L, 0, L, C, ptr(ws),
+                                                     ws.numel(), cs()), "bwd")
+        t_all, t_nodx = timeit(bwd(True), args.iters), timeit(bwd(False), args.iters)
+        res["tcn_stage_bwd"] = {"us": t_all, "us_without_dx": t_nodx, "dx_us": t_all - t_nodx,
+                                "ws_MiB": ws.numel() / 2 ** 20}
     for k, v in res.items():
         print(k, json.dumps({a: round(b, 2) if isinstance(b, float) else b for a, b in v.items()}))
 
