@@ -1265,16 +1265,38 @@ int launch_fwd(bool ut, bool save, const float* residual, const float* tfeat, co
     return LG_OK;
 }
 
+// k_gru_bwd<H, UT, DX, DHS> over `grid` 16-sequence workgroups.  DHS = false (lg_gru_bwd: dh_last
+// alone) exists with dx only, its no-dx case being k_gru_bwd2's; DHS = true (lg_gru_seq_bwd's
+// encoder form: dh_seq added at every step) with and without dx.
+template <int H, bool DHS>
+int launch_bwd_tiled(bool ut, unsigned grid, const float* residual, const float* tfeat, const float* w_ih,
+                     const float* w_hh, const float* h_seq, const float* gates, const float* dh_seq,
+                     const float* dh_last, float* dx, float* slab, int64_t Nseq, int64_t L, int64_t S, hipStream_t s) {
+    const lg_fastdiv fdS = lg_make_fastdiv(static_cast<uint32_t>(S));
+#define LG_GRU_BWD(UT, DX)                                                                                       \
+    lg_launch(k_gru_bwd<H, UT, DX, DHS>, grid, 4 * H, 0, s, residual, tfeat, w_ih, w_hh, h_seq, gates, dh_last, dx,  \
+              slab, static_cast<uint32_t>(Nseq), static_cast<int>(L), static_cast<int>(S), fdS, dh_seq)
+    if (dx) {
+        if (ut) LG_GRU_BWD(true, true); else LG_GRU_BWD(false, true);
+    } else if constexpr (DHS) {
+        if (ut) LG_GRU_BWD(true, false); else LG_GRU_BWD(false, false);
+    } else {
+        return LG_EINVAL;
+    }
+#undef LG_GRU_BWD
+    LG_RET_IF_LAUNCH_FAILED();
+    return LG_OK;
+}
+
 template <int H>
 int launch_bwd(bool ut, bool need_dx, const float* residual, const float* tfeat, const float* w_ih,
                const float* w_hh, const float* h_seq, const float* gates, const float* dh_last, float* dx,
                float* slab, int64_t B, int64_t L, int64_t S, hipStream_t s) {
+    if (need_dx)
+        return launch_bwd_tiled<H, false>(ut, static_cast<unsigned>(nblocks_seq(B * S)), residual, tfeat, w_ih, w_hh,
+                                          h_seq, gates, nullptr, dh_last, dx, slab, B * S, L, S, s);
     const uint32_t Nseq = static_cast<uint32_t>(B * S);
-    const unsigned grid = static_cast<unsigned>(nblocks_seq(B * S));
     const lg_fastdiv fdS = lg_make_fastdiv(static_cast<uint32_t>(S));
-#define LG_GRU_BWD(UT, DX)                                                                                       \
-    lg_launch(k_gru_bwd<H, UT, DX>, grid, 4 * H, 0, s, residual, tfeat, w_ih, w_hh, h_seq, gates, dh_last, dx, slab,   \
-                                                 Nseq, static_cast<int>(L), static_cast<int>(S), fdS, nullptr)
 #define LG_GRU_BWD2(UT, F, DF)                                                                                   \
     lg_launch(k_gru_bwd2<H, UT, F, DF>, static_cast<unsigned>(nblocks_seq2(B * S)), GB2<H>::NTH, 0, s, residual,    \
               tfeat, w_hh, h_seq, gates, dh_last, slab, Nseq, static_cast<int>(L), static_cast<int>(S), fdS, GruNiB{})
@@ -1293,161 +1315,21 @@ int launch_bwd(bool ut, bool need_dx, const float* residual, const float* tfeat,
         return LG_OK;
     }
 #endif
-    if (need_dx) {
-        if (ut) LG_GRU_BWD(true, true); else LG_GRU_BWD(false, true);
-    } else if (ut) {
-        LG_GRU_BWD2(true, true, true);
-    } else {
-        LG_GRU_BWD2(false, true, true);
-    }
-#undef LG_GRU_BWD
+    if (ut) LG_GRU_BWD2(true, true, true); else LG_GRU_BWD2(false, true, true);
 #undef LG_GRU_BWD2
     LG_RET_IF_LAUNCH_FAILED();
     return LG_OK;
 }
 
-// ------------------------------------------------------------------ any hidden width
-// The encoder at a hidden width the tiled kernels above do not cover (H not 32 / 64; ABI 26):
-// the same recurrence (detector.py:60-73 through nn.GRU) with one hidden unit per thread and a
-// workgroup per sequence (grid-stride over the B*S sequences), h_{t-1} and x_t in LDS, W read
-// through the caches.  Same saved layouts as the tiled kernels: h_seq [t][seq][H] = h_t and
-// gates [t][seq][4][H] = sigma(r), sigma(z), n, W_hn h_{t-1} + b_hn.  A generality path (the
-// reference's widths run the tiled kernels), sized for correctness at any H <= 1024.
-constexpr int kGenMaxH = 1024;
-constexpr int kGenBwdBlocks = 512;  // slab rows of the generic backward
-
-inline int gen_threads(int64_t H) { return static_cast<int>((H + 63) / 64 * 64); }
-
-__global__ void __launch_bounds__(kGenMaxH) k_gru_gen_fwd(const float* __restrict__ residual,
-                                                          const float* __restrict__ tfeat, const float* __restrict__ w_ih,
-                                                          const float* __restrict__ w_hh, const float* __restrict__ b_ih,
-                                                          const float* __restrict__ b_hh, float* __restrict__ h_seq,
-                                                          float* __restrict__ gates, float* __restrict__ h_last, int B,
-                                                          int L, int S, int I, int H) {
-    extern __shared__ float gsm[];
-    float* hs = gsm;      // h_{t-1} [H]
-    float* xs = gsm + H;  // x_t [I]
-    const int u = threadIdx.x;
-    const int64_t nseq = static_cast<int64_t>(B) * S;
-    for (int64_t seq = blockIdx.x; seq < nseq; seq += gridDim.x) {
-        const int64_t b = seq / S, sn = seq % S;
-        if (u < H) hs[u] = 0.f;
-        for (int t = 0; t < L; ++t) {
-            if (u < I) xs[u] = u == 0 ? residual[(b * L + t) * S + sn] : tfeat[(b * L + t) * (I - 1) + u - 1];
-            __syncthreads();
-            float hn = 0.f, g[4] = {0.f, 0.f, 0.f, 0.f};
-            if (u < H) {
-                float a[3], c[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const int row = k * H + u;
-                    a[k] = b_ih[row];
-                    for (int i = 0; i < I; ++i) a[k] = fmaf(w_ih[static_cast<int64_t>(row) * I + i], xs[i], a[k]);
-                    c[k] = b_hh[row];
-                    const float* wr = w_hh + static_cast<int64_t>(row) * H;
-                    for (int i = 0; i < H; ++i) c[k] = fmaf(wr[i], hs[i], c[k]);
-                }
-                g[0] = sigm(a[0] + c[0]);
-                g[1] = sigm(a[1] + c[1]);
-                g[2] = gru_tanh(a[2] + g[0] * c[2]);
-                g[3] = c[2];
-                hn = (1.f - g[1]) * g[2] + g[1] * hs[u];
-            }
-            __syncthreads();
-            if (u < H) {
-                hs[u] = hn;
-                const int64_t r = static_cast<int64_t>(t) * nseq + seq;
-                if (h_seq) h_seq[r * H + u] = hn;
-                if (gates) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) gates[(r * 4 + k) * H + u] = g[k];
-                }
-            }
-        }
-        if (u < H) h_last[seq * H + u] = hs[u];
-        __syncthreads();
-    }
-}
-
-// BPTT per sequence; the weight gradients accumulate into the workgroup's own slab row
-// [dW_hh 3H x H | dW_ih 3H x I | db_ih 3H | db_hh 3H] (every element read-modified-written by
-// one fixed thread: no races, no atomics), reduced over the rows in row order afterwards.
-__global__ void __launch_bounds__(kGenMaxH) k_gru_gen_bwd(const float* __restrict__ residual,
-                                                          const float* __restrict__ tfeat, const float* __restrict__ w_ih,
-                                                          const float* __restrict__ w_hh, const float* __restrict__ h_seq,
-                                                          const float* __restrict__ gates,
-                                                          const float* __restrict__ dh_last, float* __restrict__ dx,
-                                                          float* __restrict__ slab, int B, int L, int S, int I, int H) {
-    extern __shared__ float gsm[];
-    float* dh = gsm;            // dL/dh_t [H]
-    float* hp = dh + H;         // h_{t-1} [H]
-    float* dgh = hp + H;        // d(W_h. h + b_h.) [3H]
-    float* dgn = dgh + 3 * H;   // d(W_in x + b_in) [H] (the r and z parts equal dgh's)
-    float* xs = dgn + H;        // x_t [I]
-    const int u = threadIdx.x, nt = blockDim.x;
-    const int G3 = 3 * H;
-    const int64_t nseq = static_cast<int64_t>(B) * S, len = static_cast<int64_t>(G3) * (H + I) + 2 * G3;
-    float* row = slab + blockIdx.x * len;
-    float* dwhh = row;
-    float* dwih = row + static_cast<int64_t>(G3) * H;
-    float* dbih = dwih + static_cast<int64_t>(G3) * I;
-    float* dbhh = dbih + G3;
-    // each element is zeroed by the thread that accumulates it
-    if (u < H)
-        for (int j = 0; j < G3; ++j) dwhh[static_cast<int64_t>(j) * H + u] = 0.f;
-    if (u < I)
-        for (int j = 0; j < G3; ++j) dwih[static_cast<int64_t>(j) * I + u] = 0.f;
-    for (int j = u; j < G3; j += nt) dbih[j] = dbhh[j] = 0.f;
-    auto dgi = [&](int j) { return j < 2 * H ? dgh[j] : dgn[j - 2 * H]; };
-    for (int64_t seq = blockIdx.x; seq < nseq; seq += gridDim.x) {
-        const int64_t b = seq / S, sn = seq % S;
-        if (u < H) dh[u] = dh_last[seq * H + u];
-        for (int t = L - 1; t >= 0; --t) {
-            const int64_t r = static_cast<int64_t>(t) * nseq + seq;
-            if (u < I) xs[u] = u == 0 ? residual[(b * L + t) * S + sn] : tfeat[(b * L + t) * (I - 1) + u - 1];
-            float dz_keep = 0.f;
-            if (u < H) {
-                const float h0 = t > 0 ? h_seq[(r - nseq) * H + u] : 0.f;
-                hp[u] = h0;
-                const float rg = gates[(r * 4 + 0) * H + u], zg = gates[(r * 4 + 1) * H + u];
-                const float ng = gates[(r * 4 + 2) * H + u], ghn = gates[(r * 4 + 3) * H + u];
-                const float d = dh[u];
-                const float dnp = d * (1.f - zg) * (1.f - ng * ng);
-                const float dzp = d * (h0 - ng) * zg * (1.f - zg);
-                const float drp = dnp * ghn * rg * (1.f - rg);
-                dgh[u] = drp;
-                dgh[H + u] = dzp;
-                dgh[2 * H + u] = dnp * rg;
-                dgn[u] = dnp;
-                dz_keep = d * zg;
-            }
-            __syncthreads();
-            float acc = dz_keep;
-            if (u < H) {
-                for (int j = 0; j < G3; ++j) {
-                    const float gj = dgh[j];
-                    acc = fmaf(w_hh[static_cast<int64_t>(j) * H + u], gj, acc);
-                    dwhh[static_cast<int64_t>(j) * H + u] += gj * hp[u];
-                }
-            }
-            if (u < I) {
-                float dxi = 0.f;
-                for (int j = 0; j < G3; ++j) {
-                    const float gj = dgi(j);
-                    dxi = fmaf(w_ih[static_cast<int64_t>(j) * I + u], gj, dxi);
-                    dwih[static_cast<int64_t>(j) * I + u] += gj * xs[u];
-                }
-                if (dx) dx[(seq * L + t) * I + u] = dxi;
-            }
-            for (int j = u; j < G3; j += nt) {
-                dbih[j] += dgi(j);
-                dbhh[j] += dgh[j];
-            }
-            __syncthreads();
-            if (u < H) dh[u] = acc;
-        }
-        __syncthreads();
-    }
+// One reduction of a GRU backward's slab rows [dW_hh 3H x H | dW_ih 3H x I | db_ih 3H | db_hh 3H |
+// extra ...] into the gradients; `extra` are the caller's segments behind those four.
+int reduce_gru_slab(const float* slab, int nb, int64_t len, int64_t I, int64_t H, float* dw_ih, float* dw_hh,
+                    float* db_ih, float* db_hh, hipStream_t s, const LgSlabSeg* extra = nullptr, int n_extra = 0) {
+    const int64_t G3 = 3 * H, nWhh = G3 * H, nWih = G3 * I;
+    LgSlabSeg segs[6] = {{0, nWhh, dw_hh}, {nWhh, nWih, dw_ih}, {nWhh + nWih, G3, db_ih}, {nWhh + nWih + G3, G3, db_hh}};
+    if (n_extra > 2) return LG_EINVAL;
+    for (int i = 0; i < n_extra; ++i) segs[4 + i] = extra[i];
+    return lg_launch_slab_reduce_multi(slab, nb, len, segs, 4 + n_extra, nullptr, nullptr, s);
 }
 
 // ------------------------------------------------------------------ stacked layers (dense input)
@@ -1869,27 +1751,44 @@ k_gru_seq_bwd(const float* __restrict__ x, const float* __restrict__ Wih, const 
     }
 }
 
-// Any H in 1..1024 and any dense I in 1..1024, and the encoder input form (x == NULL: x_t =
-// [residual[b, t, s], tfeat[b, t, :]], I in {1, 10}, dx [Nseq][L][I]) at widths off the tiled
-// kernels: k_gru_gen_fwd / k_gru_gen_bwd's scheme (a workgroup per sequence, a hidden unit per
-// thread, input columns strided over the threads), 64-bit offsets throughout.
-__global__ void __launch_bounds__(kGenMaxH) k_gru_seq_gen_fwd(const float* __restrict__ x,
-                                                              const float* __restrict__ w_ih,
-                                                              const float* __restrict__ w_hh,
-                                                              const float* __restrict__ b_ih,
-                                                              const float* __restrict__ b_hh, float* __restrict__ h_seq,
-                                                              float* __restrict__ gates, int64_t nseq, int L, int I, int H,
-                                                              SeqDrop dr) {
+// ------------------------------------------------------------------ any hidden width
+// Every GRU layer the tiled kernels do not cover (lg_gru_fwd / lg_gru_bwd at H not 32 / 64, ABI 26;
+// lg_gru_seq_fwd / lg_gru_seq_bwd off their tiled shapes): any H in 1..1024, a dense input x
+// [L][Nseq][I] of any I in 1..1024 or the encoder input form (x == NULL: x_t = [residual[b, t, s],
+// tfeat[b, t, :]], I in {1, 10}, S sensors per window, dx [Nseq][L][I]).  The same recurrence
+// (detector.py:60-73 through nn.GRU) with one hidden unit per thread and a workgroup per sequence
+// (grid-stride over the sequences), input columns strided over the threads, h_{t-1} and x_t in LDS,
+// W read through the caches, 64-bit offsets throughout.  Same saved layouts as the tiled kernels:
+// h_seq [t][seq][H] = h_t and gates [t][seq][4][H] = sigma(r), sigma(z), n, W_hn h_{t-1} + b_hn.
+// A generality path (the reference's widths run the tiled kernels), sized for correctness.
+constexpr int kGenMaxH = 1024;
+constexpr int kGenBwdBlocks = 512;  // slab rows of the generic backward
+
+inline int gen_threads(int64_t H) { return static_cast<int>((H + 63) / 64 * 64); }
+
+// ENC: the encoder input form, where h_seq is optional and h_last [Nseq][H] (the last step's h), if
+// given, is written; the dense form requires h_seq.  A template flag, not a test of x, so the dense
+// instantiation stays the code it was before the encoder form joined it.  gates are optional.
+template <bool ENC>
+__global__ void __launch_bounds__(kGenMaxH) k_gru_seq_gen_fwd(
+    const float* __restrict__ x, const float* __restrict__ residual, const float* __restrict__ tfeat,
+    const float* __restrict__ w_ih, const float* __restrict__ w_hh, const float* __restrict__ b_ih,
+    const float* __restrict__ b_hh, float* __restrict__ h_seq, float* __restrict__ gates, float* __restrict__ h_last,
+    int64_t nseq, int L, int S, int I, int H, SeqDrop dr) {
     extern __shared__ float gsm[];
     float* hs = gsm;      // h_{t-1} [H]
     float* xs = gsm + H;  // x_eff,t [I]
     const int u = threadIdx.x, nth = blockDim.x;
     const uint32_t key = dr.on ? lg_dropout_key_dev(dr.seed, dr.salt) : 0u;
     for (int64_t seq = blockIdx.x; seq < nseq; seq += gridDim.x) {
+        const int64_t b = ENC ? seq / S : 0, sn = ENC ? seq % S : 0;
         if (u < H) hs[u] = 0.f;
         for (int t = 0; t < L; ++t) {
             const int64_t r = static_cast<int64_t>(t) * nseq + seq;
-            for (int i = u; i < I; i += nth) xs[i] = seq_drop(dr, key, x[r * I + i], static_cast<uint64_t>(r) * I + i);
+            for (int i = u; i < I; i += nth) {
+                if constexpr (ENC) xs[i] = i == 0 ? residual[(b * L + t) * S + sn] : tfeat[(b * L + t) * (I - 1) + i - 1];
+                else xs[i] = seq_drop(dr, key, x[r * I + i], static_cast<uint64_t>(r) * I + i);
+            }
             __syncthreads();
             float hn = 0.f, g[4] = {0.f, 0.f, 0.f, 0.f};
             if (u < H) {
@@ -1913,17 +1812,22 @@ __global__ void __launch_bounds__(kGenMaxH) k_gru_seq_gen_fwd(const float* __res
             __syncthreads();
             if (u < H) {
                 hs[u] = hn;
-                h_seq[r * H + u] = hn;
+                if (!ENC || h_seq) h_seq[r * H + u] = hn;
                 if (gates) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) gates[(r * 4 + k) * H + u] = g[k];
                 }
             }
         }
+        if (ENC && h_last && u < H) h_last[seq * H + u] = hs[u];
         __syncthreads();
     }
 }
 
+// BPTT per sequence; the weight gradients accumulate into the workgroup's own slab row
+// [dW_hh 3H x H | dW_ih 3H x I | db_ih 3H | db_hh 3H] (every element read-modified-written by
+// one fixed thread: no races, no atomics), reduced over the rows in row order afterwards.
+// Either of dh_seq / dh_last may be NULL: a NULL one contributes zero.
 __global__ void __launch_bounds__(kGenMaxH) k_gru_seq_gen_bwd(
     const float* __restrict__ x, const float* __restrict__ residual, const float* __restrict__ tfeat,
     const float* __restrict__ w_ih, const float* __restrict__ w_hh, const float* __restrict__ h_seq,
@@ -2067,9 +1971,9 @@ extern "C" int lg_gru_fwd(const float* residual, const float* tfeat, const float
     hipStream_t s = lg_stream(stream);
     if (H != 32 && H != 64) {  // any other width: the generic kernel
         const unsigned grid = static_cast<unsigned>(std::min<int64_t>(B * S, 4096));
-        lg_launch(k_gru_gen_fwd, grid, gen_threads(H), sizeof(float) * (H + I), s, residual, tfeat, w_ih, w_hh, b_ih,
-                  b_hh, h_seq, gates, h_last, static_cast<int>(B), static_cast<int>(L), static_cast<int>(S),
-                  static_cast<int>(I), static_cast<int>(H));
+        lg_launch(k_gru_seq_gen_fwd<true>, grid, gen_threads(H), sizeof(float) * (H + I), s, nullptr, residual, tfeat, w_ih,
+                  w_hh, b_ih, b_hh, h_seq, gates, h_last, B * S, static_cast<int>(L), static_cast<int>(S),
+                  static_cast<int>(I), static_cast<int>(H), SeqDrop{});
         LG_RET_IF_LAUNCH_FAILED();
         return LG_OK;
     }
@@ -2101,9 +2005,9 @@ extern "C" int lg_gru_bwd(const float* residual, const float* tfeat, const float
     if (B == 0) {
         if (hipMemsetAsync(slab, 0, sizeof(float) * len, s) != hipSuccess) return LG_EHIP;
     } else if (gen) {
-        lg_launch(k_gru_gen_bwd, static_cast<unsigned>(nb), gen_threads(H), sizeof(float) * (6 * H + I), s, residual,
-                  tfeat, w_ih, w_hh, h_seq, gates, dh_last, dx, slab, static_cast<int>(B), static_cast<int>(L),
-                  static_cast<int>(S), static_cast<int>(I), static_cast<int>(H));
+        lg_launch(k_gru_seq_gen_bwd, static_cast<unsigned>(nb), gen_threads(H), sizeof(float) * (6 * H + I), s, nullptr,
+                  residual, tfeat, w_ih, w_hh, h_seq, gates, nullptr, dh_last, dx, slab, B * S, static_cast<int>(L),
+                  static_cast<int>(S), static_cast<int>(I), static_cast<int>(H), SeqDrop{});
         LG_RET_IF_LAUNCH_FAILED();
     } else {
         const int rc = H == 64 ? launch_bwd<64>(I == 10, dx != nullptr, residual, tfeat, w_ih, w_hh, h_seq, gates,
@@ -2112,10 +2016,7 @@ extern "C" int lg_gru_bwd(const float* residual, const float* tfeat, const float
                                                 dh_last, dx, slab, B, L, S, s);
         if (rc != LG_OK) return rc;
     }
-    const int64_t nWhh = G3 * H, nWih = G3 * I;
-    const LgSlabSeg segs[4] = {{0, nWhh, dw_hh}, {nWhh, nWih, dw_ih}, {nWhh + nWih, G3, db_ih},
-                               {nWhh + nWih + G3, G3, db_hh}};
-    return lg_launch_slab_reduce_multi(slab, nb, len, segs, 4, nullptr, nullptr, s);
+    return reduce_gru_slab(slab, nb, len, I, H, dw_ih, dw_hh, db_ih, db_hh, s);
 }
 
 // ------------------------------------------------------------------ GRU + node init, fused
@@ -2209,10 +2110,8 @@ extern "C" int lg_gru_node_init_bwd(const float* residual, const float* tfeat, c
 #undef LG_GRU_NIB
         LG_RET_IF_LAUNCH_FAILED();
     }
-    const int64_t nWhh = G3 * H, nWih = G3 * I;
-    const LgSlabSeg segs[6] = {{0, nWhh, dw_hh}, {nWhh, nWih, dw_ih}, {nWhh + nWih, G3, db_ih},
-                               {nWhh + nWih + G3, G3, db_hh}, {gl, H * (H + 1), dproj_w}, dbseg};
-    return lg_launch_slab_reduce_multi(slab, nb, len, segs, 6, nullptr, nullptr, s);
+    const LgSlabSeg extra[2] = {{gl, H * (H + 1), dproj_w}, dbseg};
+    return reduce_gru_slab(slab, nb, len, I, H, dw_ih, dw_hh, db_ih, db_hh, s, extra, 2);
 }
 
 // ------------------------------------------------------------------ stacked layers: entry points
@@ -2251,8 +2150,9 @@ extern "C" int lg_gru_seq_fwd(const float* x, const float* w_ih, const float* w_
 #undef LG_GRU_SEQ_FWD
     } else {
         const unsigned grid = static_cast<unsigned>(std::min<int64_t>(Nseq, 4096));
-        lg_launch(k_gru_seq_gen_fwd, grid, gen_threads(H), sizeof(float) * (H + I), s, x, w_ih, w_hh, b_ih, b_hh, h_seq,
-                  gates, Nseq, static_cast<int>(L), static_cast<int>(I), static_cast<int>(H), dr);
+        lg_launch(k_gru_seq_gen_fwd<false>, grid, gen_threads(H), sizeof(float) * (H + I), s, x, nullptr, nullptr, w_ih, w_hh,
+                  b_ih, b_hh, h_seq, gates, nullptr, Nseq, static_cast<int>(L), 1, static_cast<int>(I),
+                  static_cast<int>(H), dr);
     }
     LG_RET_IF_LAUNCH_FAILED();
     return LG_OK;
@@ -2291,7 +2191,7 @@ extern "C" int lg_gru_seq_bwd(const float* x, const float* residual, const float
     }
     const bool tiled = seq_tiled(dense, I, H);
     const int nb = static_cast<int>(seq_bwd_rows(tiled, Nseq, I, H));
-    const int64_t len = seq_slab_len(I, H), G3 = 3 * H;
+    const int64_t len = seq_slab_len(I, H);
     if (ws_bytes < nb * len * static_cast<int64_t>(sizeof(float))) return LG_EINVAL;
     hipStream_t s = lg_stream(stream);
     float* slab = static_cast<float*>(workspace);
@@ -2313,26 +2213,14 @@ extern "C" int lg_gru_seq_bwd(const float* x, const float* residual, const float
 #undef LG_GRU_SEQ_BWD
         LG_RET_IF_LAUNCH_FAILED();
     } else {  // the encoder's first layer under a stack: k_gru_bwd with the per-step upstream gradient
-        const uint32_t n = static_cast<uint32_t>(Nseq);
-        const lg_fastdiv fdS = lg_make_fastdiv(static_cast<uint32_t>(S));
-#define LG_GRU_BWD_DHS(HH, UT, DX)                                                                                \
-    lg_launch(k_gru_bwd<HH, UT, DX, true>, static_cast<unsigned>(nb), 4 * HH, 0, s, residual, tfeat, w_ih, w_hh, h_seq, \
-              gates, dh_last, dx, slab, n, static_cast<int>(L), static_cast<int>(S), fdS, dh_seq)
-        const bool ut = I == 10, dxv = dx != nullptr;
-        if (H == 64) {
-            if (ut) { if (dxv) LG_GRU_BWD_DHS(64, true, true); else LG_GRU_BWD_DHS(64, true, false); }
-            else { if (dxv) LG_GRU_BWD_DHS(64, false, true); else LG_GRU_BWD_DHS(64, false, false); }
-        } else {
-            if (ut) { if (dxv) LG_GRU_BWD_DHS(32, true, true); else LG_GRU_BWD_DHS(32, true, false); }
-            else { if (dxv) LG_GRU_BWD_DHS(32, false, true); else LG_GRU_BWD_DHS(32, false, false); }
-        }
-#undef LG_GRU_BWD_DHS
-        LG_RET_IF_LAUNCH_FAILED();
+        const unsigned grid = static_cast<unsigned>(nb);
+        const int rc = H == 64 ? launch_bwd_tiled<64, true>(I == 10, grid, residual, tfeat, w_ih, w_hh, h_seq, gates,
+                                                            dh_seq, dh_last, dx, slab, Nseq, L, S, s)
+                               : launch_bwd_tiled<32, true>(I == 10, grid, residual, tfeat, w_ih, w_hh, h_seq, gates,
+                                                            dh_seq, dh_last, dx, slab, Nseq, L, S, s);
+        if (rc != LG_OK) return rc;
     }
-    const int64_t nWhh = G3 * H, nWih = G3 * I;
-    const LgSlabSeg segs[4] = {{0, nWhh, dw_hh}, {nWhh, nWih, dw_ih}, {nWhh + nWih, G3, db_ih},
-                               {nWhh + nWih + G3, G3, db_hh}};
-    return lg_launch_slab_reduce_multi(slab, nb, len, segs, 4, nullptr, nullptr, s);
+    return reduce_gru_slab(slab, nb, len, I, H, dw_ih, dw_hh, db_ih, db_hh, s);
 }
 
 extern "C" int lg_gru_seq_tiled(int64_t I, int64_t H, int backward) {

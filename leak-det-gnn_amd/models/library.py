@@ -40,7 +40,7 @@ from torch import Tensor
 from . import _native as nat
 from ._native import check, load_library, ptr, stream_of
 from .ops import (EDGE_HEAD_SALT, GCN_BWD_NM_EXTRA_FLAGS, GCN_FWD_DENSE_EXTRA_FLAGS, GCN_FWD_NM_EXTRA_FLAGS,
-                  NM_MAX_BYTES, NOLEAK_HEAD_SALT, _check_d, _timed)
+                  GRU_PRED_SALT, GRU_STACK_SALT, NM_MAX_BYTES, NOLEAK_HEAD_SALT, TCN_SALT, _check_d, _timed)
 
 NS = "leakgnn"
 
@@ -390,6 +390,171 @@ def _sensor_proj_bwd(ctx, dproj):
 sensor_proj.register_autograd(_sensor_proj_bwd, setup_context=_sensor_proj_setup)
 
 
+# ============================================================================ GRU ops: shared drivers
+# gru_encoder, gru_stack and gru_predictor are one layer loop (_gru_forward) and one BPTT loop
+# (_gru_bptt) over the C entry points.  What differs between the ops is passed in:
+#   layer-0 input       enc = (residual, tfeat) read in place (lg_gru_fwd), or a dense time-major xt
+#                       through lg_gru_seq_fwd / lg_gru_seq_bwd like every upper layer (gru_predictor)
+#   layer-0 backward    under enc, lg_gru_bwd (gru_encoder: own_l0) or lg_gru_seq_bwd's encoder form
+#   dropout salts       salt0 + boundary (GRU_STACK_SALT / GRU_PRED_SALT)
+#   top h_seq, no save  dropped where the layer can write h_last alone (keep_h False)
+#   workspace           each entry's query, plus ws_extra bytes (gru_predictor's one-pass dG at H = 128)
+def _split(ts, *lens: int) -> List[List[Tensor]]:
+    """A flat tensor sequence cut into consecutive runs of the given lengths (a + b + ... undone)."""
+    if sum(lens) != len(ts):
+        raise ValueError(f"expected {sum(lens)} tensors in runs of {lens}, got {len(ts)}")
+    runs, i = [], 0
+    for n in lens:
+        runs.append(list(ts[i:i + n]))
+        i += n
+    return runs
+
+
+def _gru_dims(op: str, x: Tensor, dense: bool, w_ih: List[Tensor], w_hh: List[Tensor],
+              b_ih: Optional[List[Tensor]] = None, b_hh: Optional[List[Tensor]] = None, p: float = 0.0
+              ) -> Tuple[int, int, int]:
+    """(I, H, layers) of a GRU op's per-layer weight lists, every shape checked.  x is the dense
+    (B, L, I) input or, not dense, residual (B, L, S) with I taken from w_ih[0]; the bias lists are
+    checked where given (the backward ops take none)."""
+    if x.dim() != 3:
+        raise ValueError(f"{op}: {'x must be (B, L, I)' if dense else 'residual must be (B, L, S)'}, "
+                         f"got {tuple(x.shape)}")
+    nl = len(w_hh)
+    if nl < 1 or any(ts is not None and len(ts) != nl for ts in (w_ih, b_ih, b_hh)):
+        raise ValueError(f"{op}: one (w_ih, w_hh, b_ih, b_hh) per layer")
+    if w_hh[0].dim() != 2 or w_ih[0].dim() != 2:
+        raise ValueError(f"{op}: w_hh must be (3H, H), got {tuple(w_hh[0].shape)}")
+    H = w_hh[0].shape[1]
+    I = x.shape[2] if dense else w_ih[0].shape[1]
+    if dense and (x.shape[1] < 1 or not (1 <= I <= 1024 and 1 <= H <= 1024)):
+        raise ValueError(f"{op}: L >= 1 and I, H in 1..1024, got L {x.shape[1]}, I {I}, H {H}")
+    for l in range(nl):
+        want = (3 * H, I if l == 0 else H)
+        if (tuple(w_ih[l].shape) != want or tuple(w_hh[l].shape) != (3 * H, H)
+                or any(b is not None and tuple(b[l].shape) != (3 * H,) for b in (b_ih, b_hh))):
+            raise ValueError(f"{op}: layer {l} weights {tuple(w_ih[l].shape)}, {tuple(w_hh[l].shape)}, biases "
+                             f"{[tuple(b[l].shape) for b in (b_ih, b_hh) if b is not None]}; expected {want}, "
+                             f"{(3 * H, H)}, {(3 * H,)}")
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{op}: dropout p must be in [0, 1), got {p}")
+    return I, H, nl
+
+
+def _layer_drop(l: int, p: float, seed: Tensor, salt0: int) -> Tuple[int, float, int, int]:
+    """(flags, p, seed, salt) of the dropout layer l reads its input through: boundary l - 1 of the
+    stack (salt0 + l - 1) for l > 0 and p > 0, none otherwise."""
+    if l == 0 or not p > 0.0:
+        return 0, 0.0, 0, 0
+    seed_v, sbit = _seed_args(seed)
+    return nat.LG_F_DROPOUT, p, seed_v, (salt0 + l - 1) | sbit
+
+
+def _gru_forward(lib, enc: Optional[Tuple[Tensor, Optional[Tensor]]], xt: Optional[Tensor], w_ih: List[Tensor],
+                 w_hh: List[Tensor], b_ih: List[Tensor], b_hh: List[Tensor], h_last: Tensor, L: int, I: int, p: float,
+                 seed: Optional[Tensor], salt0: int, save: bool, keep_h: bool) -> Tuple[List[Tensor], List[Tensor]]:
+    """The layer loop: (h_seqs, gates), one of each per layer, and h_last (Nseq * H elements, any
+    shape) filled with the top layer's last step.  Layer 0 reads enc or xt (L, Nseq, I), layer
+    l > 0 the h_seq below it through dropout boundary l - 1.  Tensors not produced are empty:
+    gates without save, and without save the top layer's h_seq unless keep_h - the top layer
+    then writes h_last alone (lg_gru_fwd, or lg_gru_seq_infer on a dense input)."""
+    H, nl = w_hh[0].shape[1], len(w_hh)
+    nseq = h_last.numel() // H
+    dev = h_last.device
+    st = stream_of(h_last)
+    if enc is not None:
+        residual, tfeat = enc
+        B, _, S = residual.shape
+        if tfeat is not None and tuple(tfeat.shape) != (B, L, 9):
+            raise ValueError(f"tfeat must be (B, L, 9), got {tuple(tfeat.shape)}")
+    h_seqs: List[Tensor] = []
+    gates: List[Tensor] = []
+    src = xt
+    for l in range(nl):
+        top = l == nl - 1
+        w = (ptr(w_ih[l]), ptr(w_hh[l]), ptr(b_ih[l]), ptr(b_hh[l]))
+        hs = torch.empty(L, nseq, H, device=dev) if (save or keep_h or not top) else None
+        g = torch.empty(L, nseq, 4, H, device=dev) if save else None
+        if l == 0 and enc is not None:
+            with _timed("gru_fwd", dev):
+                check(lib.lg_gru_fwd(ptr(residual), ptr(tfeat), *w, ptr(hs), ptr(g), ptr(h_last), B, L, S, I, H, st),
+                      "lg_gru_fwd")
+        elif hs is None:
+            with _timed("gru_seq_infer", dev):
+                check(lib.lg_gru_seq_infer(ptr(src), *w, None, ptr(h_last), nseq, L, I if l == 0 else H, H,
+                                           *_layer_drop(l, p, seed, salt0), st), "lg_gru_seq_infer")
+        else:
+            with _timed("gru_seq_fwd", dev):
+                check(lib.lg_gru_seq_fwd(ptr(src), *w, ptr(hs), ptr(g), nseq, L, I if l == 0 else H, H,
+                                         *_layer_drop(l, p, seed, salt0), st), "lg_gru_seq_fwd")
+            if top:
+                h_last.copy_(hs[L - 1].view(h_last.shape))
+        h_seqs.append(hs if hs is not None else torch.empty(0, device=dev))
+        gates.append(g if g is not None else torch.empty(0, device=dev))
+        src = hs
+    return h_seqs, gates
+
+
+def _gru_bptt(lib, label: str, enc: Optional[Tuple[Tensor, Optional[Tensor]]], xt: Optional[Tensor],
+              w_ih: List[Tensor], w_hh: List[Tensor], h_seqs: List[Tensor], gates: List[Tensor], dh: Tensor, L: int,
+              I: int, p: float, seed: Optional[Tensor], salt0: int, need_dx: bool, own_l0: bool = False,
+              ws_extra: int = 0) -> List[Tensor]:
+    """BPTT down the layers: [dx or empty, dW_ih_0 .., dW_hh_0 .., db_ih_0 .., db_hh_0 ..].  The top
+    layer takes dh (the gradient of h_L) alone, each layer's dx is the layer below's per-step
+    gradient.  Layer 0 reads enc in place and writes dx (Nseq, L, I) - through lg_gru_bwd if
+    own_l0 (one layer only), else lg_gru_seq_bwd's encoder form - or reads the dense xt and
+    writes dx time-major (L, Nseq, I).  All slab reductions are one batch."""
+    H, nl = w_hh[0].shape[1], len(w_hh)
+    nseq = dh.numel() // H
+    dev = dh.device
+    st = stream_of(dh)
+    if enc is not None:
+        residual, tfeat = enc
+        B, _, S = residual.shape
+    dw_ih, dw_hh = [torch.empty_like(t) for t in w_ih], [torch.empty_like(t) for t in w_hh]
+    db_ih = [torch.empty(3 * H, device=dev) for _ in range(nl)]
+    db_hh = [torch.empty(3 * H, device=dev) for _ in range(nl)]
+    dx_shape = (nseq, L, I) if enc is not None else (L, nseq, I)
+    dx = torch.empty(dx_shape if need_dx else 0, device=dev)
+    wss = [torch.empty(int(lib.lg_gru_bwd_workspace_bytes(B, S, I, H)) if own_l0 else
+                       int(lib.lg_gru_seq_bwd_workspace_bytes(nseq, I if l == 0 else H, H)) + ws_extra,
+                       device=dev, dtype=torch.uint8) for l in range(nl)]
+    dh_seq: Optional[Tensor] = None  # the layer above's dx
+    with _reduce_batch(lib, st), _timed(label, dev):
+        for l in range(nl - 1, -1, -1):
+            dh_l = ptr(dh) if l == nl - 1 else None
+            dxl = dx if l == 0 else torch.empty(L, nseq, H, device=dev)
+            dxp = ptr(dxl) if (l > 0 or need_dx) else None
+            w = (ptr(w_ih[l]), ptr(w_hh[l]), ptr(h_seqs[l]), ptr(gates[l]))
+            dw = (ptr(dw_ih[l]), ptr(dw_hh[l]), ptr(db_ih[l]), ptr(db_hh[l]))
+            if l > 0 or enc is None:
+                check(lib.lg_gru_seq_bwd(ptr(xt if l == 0 else h_seqs[l - 1]), None, None, *w, ptr(dh_seq), dh_l, dxp,
+                                         *dw, 0, 0, nseq, L, I if l == 0 else H, H, *_layer_drop(l, p, seed, salt0),
+                                         ptr(wss[l]), wss[l].numel(), st), "lg_gru_seq_bwd")
+            elif own_l0:
+                check(lib.lg_gru_bwd(ptr(residual), ptr(tfeat), *w, dh_l, dxp, *dw, B, L, S, I, H, ptr(wss[0]),
+                                     wss[0].numel(), st), "lg_gru_bwd")
+            else:
+                check(lib.lg_gru_seq_bwd(None, ptr(residual), ptr(tfeat), *w, ptr(dh_seq), dh_l, dxp, *dw, B, S, nseq,
+                                         L, I, H, 0, 0.0, 0, 0, ptr(wss[0]), wss[0].numel(), st), "lg_gru_seq_bwd")
+            dh_seq = dxl
+    return [dx] + dw_ih + dw_hh + db_ih + db_hh
+
+
+def _gru_bptt_fake(dx: Tensor, w_ih: List[Tensor], w_hh: List[Tensor]) -> List[Tensor]:
+    H = w_hh[0].shape[1]
+    return ([dx] + [torch.empty_like(t) for t in w_ih] + [torch.empty_like(t) for t in w_hh]
+            + [dx.new_empty(3 * H) for _ in range(2 * len(w_hh))])
+
+
+def _unfold_dx(dx: Tensor, residual: Tensor, need_res: bool, need_tf: bool) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """(d residual (B, L, S), d tfeat (B, L, I - 1)) of the encoder input's dx (B*S, L, I): column 0 is
+    the sensor's residual, the others the window's time features, shared by its S sequences."""
+    B, L, S = residual.shape
+    dres = dx[..., 0].reshape(B, S, L).transpose(1, 2) if need_res else None
+    dtf = dx[..., 1:].reshape(B, S, L, dx.shape[-1] - 1).sum(dim=1) if need_tf else None
+    return dres, dtf
+
+
 # ============================================================================ gru_encoder
 @torch.library.custom_op(f"{NS}::gru_encoder", mutates_args=(), device_types="cuda")
 def gru_encoder(residual: Tensor, tfeat: Optional[Tensor], w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor,
@@ -401,19 +566,10 @@ def gru_encoder(residual: Tensor, tfeat: Optional[Tensor], w_ih: Tensor, w_hh: T
     residual, tfeat, w_ih, w_hh, b_ih, b_hh = (_c(t) for t in (residual, tfeat, w_ih, w_hh, b_ih, b_hh))
     _req(residual, tfeat, w_ih, w_hh, b_ih, b_hh)
     B, L, S = residual.shape
-    G, I = w_ih.shape
-    H = w_hh.shape[1]
-    if tfeat is not None and tuple(tfeat.shape) != (B, L, 9):
-        raise ValueError(f"tfeat must be (B, L, 9), got {tuple(tfeat.shape)}")
-    dev = residual.device
-    h_seq = torch.empty(L, B * S, H, device=dev) if save else torch.empty(0, device=dev)
-    gates = torch.empty(L, B * S, 4, H, device=dev) if save else torch.empty(0, device=dev)
-    h_last = torch.empty(B, S, H, device=dev)
-    with _timed("gru_fwd", dev):
-        check(lib.lg_gru_fwd(ptr(residual), ptr(tfeat), ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh),
-                             ptr(h_seq) if save else None, ptr(gates) if save else None, ptr(h_last), B, L, S, I, H,
-                             stream_of(residual)), "lg_gru_fwd")
-    return h_last, h_seq, gates
+    h_last = torch.empty(B, S, w_hh.shape[1], device=residual.device)
+    h_seqs, gates = _gru_forward(lib, (residual, tfeat), None, [w_ih], [w_hh], [b_ih], [b_hh], h_last, L,
+                                 w_ih.shape[1], 0.0, None, 0, save, keep_h=False)
+    return h_last, h_seqs[0], gates[0]
 
 
 @gru_encoder.register_fake
@@ -436,27 +592,16 @@ def gru_encoder_backward(dh: Tensor, residual: Tensor, tfeat: Optional[Tensor], 
     _req(dh, residual, tfeat, w_ih, w_hh)
     if h_seq.numel() == 0 or gates.numel() == 0:
         raise RuntimeError("gru_encoder was run with save=False; no backward")
-    B, L, S = residual.shape
-    G, I = w_ih.shape
-    H = w_hh.shape[1]
-    dev = residual.device
-    dx = torch.empty(B * S, L, I, device=dev) if need_dx else torch.empty(0, device=dev)
-    dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
-    db_ih, db_hh = torch.empty(3 * H, device=dev), torch.empty(3 * H, device=dev)
-    ws = torch.empty(int(lib.lg_gru_bwd_workspace_bytes(B, S, I, H)), device=dev, dtype=torch.uint8)
-    with _reduce_batch(lib, stream_of(residual)), _timed("gru_bwd", dev):
-        check(lib.lg_gru_bwd(ptr(residual), ptr(tfeat), ptr(w_ih), ptr(w_hh), ptr(h_seq), ptr(gates), ptr(dh),
-                             ptr(dx) if need_dx else None, ptr(dw_ih), ptr(dw_hh), ptr(db_ih), ptr(db_hh), B, L, S, I,
-                             H, ptr(ws), ws.numel(), stream_of(residual)), "lg_gru_bwd")
+    dx, dw_ih, dw_hh, db_ih, db_hh = _gru_bptt(lib, "gru_bwd", (residual, tfeat), None, [w_ih], [w_hh], [h_seq], [gates],
+                                               dh, residual.shape[1], w_ih.shape[1], 0.0, None, 0, need_dx, own_l0=True)
     return dx, dw_ih, dw_hh, db_ih, db_hh
 
 
 @gru_encoder_backward.register_fake
 def _(dh, residual, tfeat, w_ih, w_hh, h_seq, gates, need_dx):
     B, L, S = residual.shape
-    H = w_hh.shape[1]
     dx = residual.new_empty(B * S, L, w_ih.shape[1]) if need_dx else residual.new_empty(0)
-    return dx, torch.empty_like(w_ih), torch.empty_like(w_hh), w_ih.new_empty(3 * H), w_ih.new_empty(3 * H)
+    return tuple(_gru_bptt_fake(dx, [w_ih], [w_hh]))
 
 
 def _gru_setup(ctx, inputs, output):
@@ -472,16 +617,10 @@ def _gru_bwd(ctx, dh, _dhseq, _dgates):
     if dh is None:
         return (None,) * 7
     residual, tfeat, w_ih, w_hh, h_seq, gates = ctx.saved_tensors
-    B, L, S = residual.shape
-    I = w_ih.shape[1]
     need_dx = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
     dx, dw_ih, dw_hh, db_ih, db_hh = torch.ops.leakgnn.gru_encoder_backward(
         dh.contiguous(), residual, tfeat if ctx.has_tfeat else None, w_ih, w_hh, h_seq, gates, need_dx)
-    dres = dtf = None
-    if ctx.needs_input_grad[0]:
-        dres = dx[..., 0].reshape(B, S, L).transpose(1, 2)
-    if ctx.has_tfeat and ctx.needs_input_grad[1]:
-        dtf = dx[..., 1:].reshape(B, S, L, I - 1).sum(dim=1)
+    dres, dtf = _unfold_dx(dx, residual, ctx.needs_input_grad[0], ctx.has_tfeat and ctx.needs_input_grad[1])
     return dres, dtf, dw_ih, dw_hh, db_ih, db_hh, None
 
 
@@ -492,20 +631,6 @@ gru_encoder.register_autograd(_gru_bwd, setup_context=_gru_setup)
 # nn.GRU(num_layers > 1) of the sensor encoder: layer 0 through lg_gru_fwd exactly as
 # gru_encoder runs it, every upper layer through lg_gru_seq_fwd on the h_seq the layer below
 # saved (no copy), inter-layer dropout applied on read (GRU_STACK_SALT + boundary).
-def _stack_dims(residual: Tensor, w_ih: List[Tensor], w_hh: List[Tensor]) -> Tuple[int, int, int, int, int, int]:
-    B, L, S = residual.shape
-    H = w_hh[0].shape[1]
-    nl = len(w_hh)
-    if nl < 1 or not (len(w_ih) == nl):
-        raise ValueError("gru_stack: one (w_ih, w_hh, b_ih, b_hh) per layer")
-    for l in range(nl):
-        want = (3 * H, w_ih[0].shape[1] if l == 0 else H)
-        if tuple(w_ih[l].shape) != want or tuple(w_hh[l].shape) != (3 * H, H):
-            raise ValueError(f"gru_stack: layer {l} weights {tuple(w_ih[l].shape)}, {tuple(w_hh[l].shape)}, "
-                             f"expected {want}, {(3 * H, H)}")
-    return B, L, S, w_ih[0].shape[1], H, nl
-
-
 @torch.library.custom_op(f"{NS}::gru_stack", mutates_args=(), device_types="cuda")
 def gru_stack(residual: Tensor, tfeat: Optional[Tensor], w_ih: List[Tensor], w_hh: List[Tensor], b_ih: List[Tensor],
               b_hh: List[Tensor], p: float, seed: Tensor, save: bool) -> List[Tensor]:
@@ -513,37 +638,16 @@ def gru_stack(residual: Tensor, tfeat: Optional[Tensor], w_ih: List[Tensor], w_h
     GRU over the B*S sensor sequences.  p > 0: dropout between layers (train mode), mask of
     boundary l (between layers l and l + 1) from (seed, GRU_STACK_SALT + l) over element index
     (t * B*S + seq) * H + i.  save: keep every layer's gates for the backward (else they are
-    empty; the lower layers' h_seq are the upper layers' input either way)."""
-    from .ops import GRU_STACK_SALT
+    empty; every layer's h_seq is kept either way)."""
     lib = load_library()
     residual, tfeat = _c(residual), _c(tfeat)
     w_ih, w_hh, b_ih, b_hh = ([_c(t) for t in ts] for ts in (w_ih, w_hh, b_ih, b_hh))
     _req(residual, tfeat, *w_ih, *w_hh, *b_ih, *b_hh)
-    B, L, S, I, H, nl = _stack_dims(residual, w_ih, w_hh)
-    if tfeat is not None and tuple(tfeat.shape) != (B, L, 9):
-        raise ValueError(f"tfeat must be (B, L, 9), got {tuple(tfeat.shape)}")
-    if not 0.0 <= p < 1.0:
-        raise ValueError(f"gru_stack: dropout p must be in [0, 1), got {p}")
-    dev = residual.device
-    st = stream_of(residual)
-    nseq = B * S
-    drop = p > 0.0
-    seed_v, sbit = _seed_args(seed) if drop else (0, 0)
-    h_seqs = [torch.empty(L, nseq, H, device=dev) for _ in range(nl)]
-    gates = [torch.empty(L, nseq, 4, H, device=dev) if save else torch.empty(0, device=dev) for _ in range(nl)]
-    h_last = torch.empty(B, S, H, device=dev)
-    with _timed("gru_fwd", dev):
-        check(lib.lg_gru_fwd(ptr(residual), ptr(tfeat), ptr(w_ih[0]), ptr(w_hh[0]), ptr(b_ih[0]), ptr(b_hh[0]),
-                             ptr(h_seqs[0]), ptr(gates[0]) if save else None, ptr(h_last), B, L, S, I, H, st),
-              "lg_gru_fwd")
-    for l in range(1, nl):
-        with _timed("gru_seq_fwd", dev):
-            check(lib.lg_gru_seq_fwd(ptr(h_seqs[l - 1]), ptr(w_ih[l]), ptr(w_hh[l]), ptr(b_ih[l]), ptr(b_hh[l]),
-                                     ptr(h_seqs[l]), ptr(gates[l]) if save else None, nseq, L, H, H,
-                                     nat.LG_F_DROPOUT if drop else 0, p, seed_v, (GRU_STACK_SALT + l - 1) | sbit, st),
-                  "lg_gru_seq_fwd")
-    if nl > 1:  # lg_gru_fwd requires its h_last; the buffer is reused for the top layer's last step
-        h_last.copy_(h_seqs[-1][L - 1].view(B, S, H))
+    I, H, _ = _gru_dims("gru_stack", residual, False, w_ih, w_hh, b_ih, b_hh, p)
+    B, L, S = residual.shape
+    h_last = torch.empty(B, S, H, device=residual.device)
+    h_seqs, gates = _gru_forward(lib, (residual, tfeat), None, w_ih, w_hh, b_ih, b_hh, h_last, L, I, p, seed,
+                                 GRU_STACK_SALT, save, keep_h=True)
     return [h_last] + h_seqs + gates
 
 
@@ -561,61 +665,27 @@ def gru_stack_backward(dh: Tensor, residual: Tensor, tfeat: Optional[Tensor], w_
                        h_seqs: List[Tensor], gates: List[Tensor], p: float, seed: Tensor, need_dx: bool
                        ) -> List[Tensor]:
     """[dx (B*S, L, I) or empty, dW_ih_0 .., dW_hh_0 .., db_ih_0 .., db_hh_0 ..]: BPTT down the stack
-    (lg_gru_seq_bwd).  The top layer takes dh (the gradient of h_L) alone, each layer's dx is the
-    layer below's per-step gradient, layer 0 reads (residual, tfeat) in place."""
-    from .ops import GRU_STACK_SALT
+    (lg_gru_seq_bwd at every layer, layer 0 in its encoder form reading (residual, tfeat) in place)."""
     lib = load_library()
     dh, residual, tfeat = _c(dh), _c(residual), _c(tfeat)
     w_ih, w_hh = [_c(t) for t in w_ih], [_c(t) for t in w_hh]
     _req(dh, residual, tfeat, *w_ih, *w_hh)
     if any(g.numel() == 0 for g in gates):
         raise RuntimeError("gru_stack was run with save=False; no backward")
-    B, L, S, I, H, nl = _stack_dims(residual, w_ih, w_hh)
-    dev = residual.device
-    st = stream_of(residual)
-    nseq = B * S
-    drop = p > 0.0
-    seed_v, sbit = _seed_args(seed) if drop else (0, 0)
-    dw_ih, dw_hh = [torch.empty_like(t) for t in w_ih], [torch.empty_like(t) for t in w_hh]
-    db_ih = [torch.empty(3 * H, device=dev) for _ in range(nl)]
-    db_hh = [torch.empty(3 * H, device=dev) for _ in range(nl)]
-    dx = torch.empty(nseq, L, I, device=dev) if need_dx else torch.empty(0, device=dev)
-    wss = [torch.empty(int(lib.lg_gru_seq_bwd_workspace_bytes(nseq, I if l == 0 else H, H)), device=dev,
-                       dtype=torch.uint8) for l in range(nl)]
-    dh_seq: Optional[Tensor] = None  # the layer above's dx
-    with _reduce_batch(lib, st), _timed("gru_bwd", dev):
-        for l in range(nl - 1, -1, -1):
-            top = l == nl - 1
-            if l > 0:
-                dxl = torch.empty(L, nseq, H, device=dev)
-                check(lib.lg_gru_seq_bwd(ptr(h_seqs[l - 1]), None, None, ptr(w_ih[l]), ptr(w_hh[l]), ptr(h_seqs[l]),
-                                         ptr(gates[l]), ptr(dh_seq), ptr(dh) if top else None, ptr(dxl), ptr(dw_ih[l]),
-                                         ptr(dw_hh[l]), ptr(db_ih[l]), ptr(db_hh[l]), 0, 0, nseq, L, H, H,
-                                         nat.LG_F_DROPOUT if drop else 0, p, seed_v, (GRU_STACK_SALT + l - 1) | sbit,
-                                         ptr(wss[l]), wss[l].numel(), st), "lg_gru_seq_bwd")
-                dh_seq = dxl
-            else:
-                check(lib.lg_gru_seq_bwd(None, ptr(residual), ptr(tfeat), ptr(w_ih[0]), ptr(w_hh[0]), ptr(h_seqs[0]),
-                                         ptr(gates[0]), ptr(dh_seq), ptr(dh) if top else None,
-                                         ptr(dx) if need_dx else None, ptr(dw_ih[0]), ptr(dw_hh[0]), ptr(db_ih[0]),
-                                         ptr(db_hh[0]), B, S, nseq, L, I, H, 0, 0.0, 0, 0, ptr(wss[0]),
-                                         wss[0].numel(), st), "lg_gru_seq_bwd")
-    return [dx] + dw_ih + dw_hh + db_ih + db_hh
+    I, _, _ = _gru_dims("gru_stack", residual, False, w_ih, w_hh)
+    return _gru_bptt(lib, "gru_bwd", (residual, tfeat), None, w_ih, w_hh, h_seqs, gates, dh, residual.shape[1], I, p,
+                     seed, GRU_STACK_SALT, need_dx)
 
 
 @gru_stack_backward.register_fake
 def _(dh, residual, tfeat, w_ih, w_hh, h_seqs, gates, p, seed, need_dx):
     B, L, S = residual.shape
-    H = w_hh[0].shape[1]
-    dx = residual.new_empty(B * S, L, w_ih[0].shape[1]) if need_dx else residual.new_empty(0)
-    return ([dx] + [torch.empty_like(t) for t in w_ih] + [torch.empty_like(t) for t in w_hh]
-            + [residual.new_empty(3 * H) for _ in range(2 * len(w_hh))])
+    return _gru_bptt_fake(residual.new_empty(B * S, L, w_ih[0].shape[1]) if need_dx else residual.new_empty(0), w_ih, w_hh)
 
 
 def _gru_stack_setup(ctx, inputs, output):
     residual, tfeat, w_ih, w_hh, _, _, p, seed, _ = inputs
-    nl = len(w_hh)
-    ctx.nl, ctx.p, ctx.has_tfeat = nl, p, tfeat is not None
+    ctx.nl, ctx.p, ctx.has_tfeat = len(w_hh), p, tfeat is not None
     ctx.mark_non_differentiable(*output[1:])
     ctx.set_materialize_grads(False)
     ctx.save_for_backward(residual, tfeat if tfeat is not None else residual, seed, *w_ih, *w_hh, *output[1:])
@@ -626,23 +696,12 @@ def _gru_stack_bwd(ctx, grads):
     if dh is None:
         return (None,) * 9
     nl = ctx.nl
-    sv = ctx.saved_tensors
-    residual, tfeat, seed = sv[:3]
-    w_ih, w_hh = list(sv[3:3 + nl]), list(sv[3 + nl:3 + 2 * nl])
-    h_seqs, gates = list(sv[3 + 2 * nl:3 + 3 * nl]), list(sv[3 + 3 * nl:])
-    B, L, S = residual.shape
-    I = w_ih[0].shape[1]
-    need_dx = ctx.needs_input_grad[0] or (ctx.has_tfeat and ctx.needs_input_grad[1])
+    (residual, tfeat, seed), w_ih, w_hh, h_seqs, gates = _split(ctx.saved_tensors, 3, nl, nl, nl, nl)
+    need_tf = ctx.has_tfeat and ctx.needs_input_grad[1]
     out = torch.ops.leakgnn.gru_stack_backward(dh.contiguous(), residual, tfeat if ctx.has_tfeat else None, w_ih, w_hh,
-                                               h_seqs, gates, ctx.p, seed, need_dx)
-    dx = out[0]
-    dres = dtf = None
-    if ctx.needs_input_grad[0]:
-        dres = dx[..., 0].reshape(B, S, L).transpose(1, 2)
-    if ctx.has_tfeat and ctx.needs_input_grad[1]:
-        dtf = dx[..., 1:].reshape(B, S, L, I - 1).sum(dim=1)
-    g = out[1:]
-    return (dres, dtf, list(g[:nl]), list(g[nl:2 * nl]), list(g[2 * nl:3 * nl]), list(g[3 * nl:]), None, None, None)
+                                               h_seqs, gates, ctx.p, seed, ctx.needs_input_grad[0] or need_tf)
+    (dx,), *dws = _split(out, 1, nl, nl, nl, nl)
+    return (*_unfold_dx(dx, residual, ctx.needs_input_grad[0], need_tf), *dws, None, None, None)
 
 
 gru_stack.register_autograd(_gru_stack_bwd, setup_context=_gru_stack_setup)
@@ -653,28 +712,6 @@ gru_stack.register_autograd(_gru_stack_bwd, setup_context=_gru_stack_setup)
 # input: every layer through lg_gru_seq_fwd / lg_gru_seq_bwd (MFMA kernels at H = 128, the
 # generic kernels at other widths), the input copied once to time-major, inter-layer dropout
 # applied on read (GRU_PRED_SALT + boundary).
-def _predictor_dims(x: Tensor, w_ih: List[Tensor], w_hh: List[Tensor], b_ih: List[Tensor], b_hh: List[Tensor]
-                    ) -> Tuple[int, int, int, int, int]:
-    if x.dim() != 3:
-        raise ValueError(f"gru_predictor: x must be (B, L, I), got {tuple(x.shape)}")
-    B, L, I = x.shape
-    nl = len(w_hh)
-    if nl < 1 or not (len(w_ih) == len(b_ih) == len(b_hh) == nl):
-        raise ValueError("gru_predictor: one (w_ih, w_hh, b_ih, b_hh) per layer")
-    if w_hh[0].dim() != 2:
-        raise ValueError(f"gru_predictor: w_hh must be (3H, H), got {tuple(w_hh[0].shape)}")
-    H = w_hh[0].shape[1]
-    if L < 1 or not (1 <= I <= 1024 and 1 <= H <= 1024):
-        raise ValueError(f"gru_predictor: L >= 1 and I, H in 1..1024, got L {L}, I {I}, H {H}")
-    for l in range(nl):
-        want = (3 * H, I if l == 0 else H)
-        if (tuple(w_ih[l].shape) != want or tuple(w_hh[l].shape) != (3 * H, H) or tuple(b_ih[l].shape) != (3 * H,)
-                or tuple(b_hh[l].shape) != (3 * H,)):
-            raise ValueError(f"gru_predictor: layer {l} weights {tuple(w_ih[l].shape)}, {tuple(w_hh[l].shape)}, biases "
-                             f"{tuple(b_ih[l].shape)}, {tuple(b_hh[l].shape)}; expected {want}, {(3 * H, H)}, {(3 * H,)}")
-    return B, L, I, H, nl
-
-
 @torch.library.custom_op(f"{NS}::gru_predictor", mutates_args=(), device_types="cuda")
 def gru_predictor(x: Tensor, w_ih: List[Tensor], w_hh: List[Tensor], b_ih: List[Tensor], b_hh: List[Tensor],
                   p: float, seed: Tensor, save: bool) -> List[Tensor]:
@@ -682,48 +719,17 @@ def gru_predictor(x: Tensor, w_ih: List[Tensor], w_hh: List[Tensor], b_ih: List[
     gates_{n-1}].  p > 0: dropout between layers, mask of boundary l from (seed, GRU_PRED_SALT + l)
     over element index (t * B + b) * H + i.  save=False (inference): no gates, and at H = 128 the
     top layer writes h_L alone (lg_gru_seq_infer); the tensors not produced are empty."""
-    from .ops import GRU_PRED_SALT
     lib = load_library()
     x = _c(x)
     w_ih, w_hh, b_ih, b_hh = ([_c(t) for t in ts] for ts in (w_ih, w_hh, b_ih, b_hh))
     _req(x, *w_ih, *w_hh, *b_ih, *b_hh)
-    B, L, I, H, nl = _predictor_dims(x, w_ih, w_hh, b_ih, b_hh)
-    if not 0.0 <= p < 1.0:
-        raise ValueError(f"gru_predictor: dropout p must be in [0, 1), got {p}")
-    dev = x.device
-    st = stream_of(x)
-    drop = p > 0.0
-    seed_v, sbit = _seed_args(seed) if drop else (0, 0)
+    I, H, _ = _gru_dims("gru_predictor", x, True, w_ih, w_hh, b_ih, b_hh, p)
+    B, L, _ = x.shape
     xt = x.transpose(0, 1).clone(memory_format=torch.contiguous_format)  # never a view of x
-    h_last = torch.empty(B, H, device=dev)
-    h_seqs: List[Tensor] = []
-    gates: List[Tensor] = []
-    src = xt
-    for l in range(nl):
-        top = l == nl - 1
-        fl = nat.LG_F_DROPOUT if (drop and l > 0) else 0
-        salt = ((GRU_PRED_SALT + l - 1) | sbit) if fl else 0
-        Il = I if l == 0 else H
-        if top and not save and H == 128:
-            with _timed("gru_seq_infer", dev):
-                check(lib.lg_gru_seq_infer(ptr(src), ptr(w_ih[l]), ptr(w_hh[l]), ptr(b_ih[l]), ptr(b_hh[l]), None,
-                                           ptr(h_last), B, L, Il, H, fl, p if fl else 0.0, seed_v if fl else 0, salt, st),
-                      "lg_gru_seq_infer")
-            h_seqs.append(torch.empty(0, device=dev))
-            gates.append(torch.empty(0, device=dev))
-            continue
-        hs = torch.empty(L, B, H, device=dev)
-        g = torch.empty(L, B, 4, H, device=dev) if save else torch.empty(0, device=dev)
-        with _timed("gru_seq_fwd", dev):
-            check(lib.lg_gru_seq_fwd(ptr(src), ptr(w_ih[l]), ptr(w_hh[l]), ptr(b_ih[l]), ptr(b_hh[l]), ptr(hs),
-                                     ptr(g) if save else None, B, L, Il, H, fl, p if fl else 0.0, seed_v if fl else 0,
-                                     salt, st), "lg_gru_seq_fwd")
-        h_seqs.append(hs)
-        gates.append(g)
-        src = hs
-        if top:
-            h_last.copy_(hs[L - 1])
-    return [h_last, xt if save else torch.empty(0, device=dev)] + h_seqs + gates
+    h_last = torch.empty(B, H, device=x.device)
+    h_seqs, gates = _gru_forward(lib, None, xt, w_ih, w_hh, b_ih, b_hh, h_last, L, I, p, seed, GRU_PRED_SALT, save,
+                                 keep_h=H != 128)
+    return [h_last, xt if save else torch.empty(0, device=x.device)] + h_seqs + gates
 
 
 @gru_predictor.register_fake
@@ -742,9 +748,7 @@ def _(x, w_ih, w_hh, b_ih, b_hh, p, seed, save):
 def gru_predictor_backward(dh: Tensor, xt: Tensor, w_ih: List[Tensor], w_hh: List[Tensor], h_seqs: List[Tensor],
                            gates: List[Tensor], p: float, seed: Tensor, need_dx: bool) -> List[Tensor]:
     """[dx (B, L, I) or empty, dW_ih_0 .., dW_hh_0 .., db_ih_0 .., db_hh_0 ..]: BPTT down the stack
-    (lg_gru_seq_bwd).  Only the top layer takes dh (the gradient of h_L); each layer's dx is the
-    layer below's per-step gradient."""
-    from .ops import GRU_PRED_SALT
+    (lg_gru_seq_bwd), dx transposed back from time-major."""
     lib = load_library()
     dh = _c(dh)
     w_ih, w_hh = [_c(t) for t in w_ih], [_c(t) for t in w_hh]
@@ -753,45 +757,18 @@ def gru_predictor_backward(dh: Tensor, xt: Tensor, w_ih: List[Tensor], w_hh: Lis
         raise RuntimeError("gru_predictor was run with save=False; no backward")
     L, B, I = xt.shape
     H = w_hh[0].shape[1]
-    nl = len(w_hh)
-    dev = xt.device
-    st = stream_of(xt)
-    drop = p > 0.0
-    seed_v, sbit = _seed_args(seed) if drop else (0, 0)
-    dw_ih, dw_hh = [torch.empty_like(t) for t in w_ih], [torch.empty_like(t) for t in w_hh]
-    db_ih = [torch.empty(3 * H, device=dev) for _ in range(nl)]
-    db_hh = [torch.empty(3 * H, device=dev) for _ in range(nl)]
-    dxt = torch.empty(L, B, I, device=dev) if need_dx else torch.empty(0, device=dev)
     # the H = 128 backward takes its dG a pass of steps at a time: room for all L steps makes it one pass
-    extra = L * B * 4 * H * 4 if H == 128 else 0
-    wss = [torch.empty(int(lib.lg_gru_seq_bwd_workspace_bytes(B, I if l == 0 else H, H)) + extra, device=dev,
-                       dtype=torch.uint8) for l in range(nl)]
-    dh_seq: Optional[Tensor] = None
-    with _reduce_batch(lib, st), _timed("gru_seq_bwd", dev):
-        for l in range(nl - 1, -1, -1):
-            top = l == nl - 1
-            fl = nat.LG_F_DROPOUT if (drop and l > 0) else 0
-            salt = ((GRU_PRED_SALT + l - 1) | sbit) if fl else 0
-            src = xt if l == 0 else h_seqs[l - 1]
-            dxl = dxt if l == 0 else torch.empty(L, B, H, device=dev)
-            want_dx = l > 0 or need_dx
-            check(lib.lg_gru_seq_bwd(ptr(src), None, None, ptr(w_ih[l]), ptr(w_hh[l]), ptr(h_seqs[l]), ptr(gates[l]),
-                                     ptr(dh_seq), ptr(dh) if top else None, ptr(dxl) if want_dx else None,
-                                     ptr(dw_ih[l]), ptr(dw_hh[l]), ptr(db_ih[l]), ptr(db_hh[l]), 0, 0, B, L,
-                                     I if l == 0 else H, H, fl, p if fl else 0.0, seed_v if fl else 0, salt,
-                                     ptr(wss[l]), wss[l].numel(), st), "lg_gru_seq_bwd")
-            dh_seq = dxl
-    dx = dxt.transpose(0, 1).contiguous() if need_dx else dxt
-    return [dx] + dw_ih + dw_hh + db_ih + db_hh
+    out = _gru_bptt(lib, "gru_seq_bwd", None, xt, w_ih, w_hh, h_seqs, gates, dh, L, I, p, seed, GRU_PRED_SALT, need_dx,
+                    ws_extra=L * B * 4 * H * 4 if H == 128 else 0)
+    if need_dx:
+        out[0] = out[0].transpose(0, 1).contiguous()
+    return out
 
 
 @gru_predictor_backward.register_fake
 def _(dh, xt, w_ih, w_hh, h_seqs, gates, p, seed, need_dx):
     L, B, I = xt.shape
-    H = w_hh[0].shape[1]
-    dx = xt.new_empty(B, L, I) if need_dx else xt.new_empty(0)
-    return ([dx] + [torch.empty_like(t) for t in w_ih] + [torch.empty_like(t) for t in w_hh]
-            + [xt.new_empty(3 * H) for _ in range(2 * len(w_hh))])
+    return _gru_bptt_fake(xt.new_empty(B, L, I) if need_dx else xt.new_empty(0), w_ih, w_hh)
 
 
 def _gru_predictor_setup(ctx, inputs, output):
@@ -807,16 +784,11 @@ def _gru_predictor_bwd(ctx, grads):
     if dh is None:
         return (None,) * 8
     nl = ctx.nl
-    sv = ctx.saved_tensors
-    seed = sv[0]
-    w_ih, w_hh = list(sv[1:1 + nl]), list(sv[1 + nl:1 + 2 * nl])
-    xt = sv[1 + 2 * nl]
-    h_seqs, gates = list(sv[2 + 2 * nl:2 + 3 * nl]), list(sv[2 + 3 * nl:])
+    (seed,), w_ih, w_hh, (xt,), h_seqs, gates = _split(ctx.saved_tensors, 1, nl, nl, 1, nl, nl)
     need_dx = ctx.needs_input_grad[0]
     out = torch.ops.leakgnn.gru_predictor_backward(dh.contiguous(), xt, w_ih, w_hh, h_seqs, gates, ctx.p, seed, need_dx)
-    g = out[1:]
-    return (out[0] if need_dx else None, list(g[:nl]), list(g[nl:2 * nl]), list(g[2 * nl:3 * nl]), list(g[3 * nl:]),
-            None, None, None)
+    (dx,), *dws = _split(out, 1, nl, nl, nl, nl)
+    return (dx if need_dx else None, *dws, None, None, None)
 
 
 gru_predictor.register_autograd(_gru_predictor_bwd, setup_context=_gru_predictor_setup)
@@ -887,7 +859,6 @@ def tcn_predictor(x: Tensor, conv_w: List[Tensor], conv_b: List[Tensor], ln_w: L
     conv stages with dilation 2 ** (i // 2).  s_i (B * L, 128) is stage i's output before the residual
     add, xhat_i / rstd_i its normalised conv output and 1 / sqrt(var + eps) (the LayerNorm backward's
     inputs).  save=False (no backward): only h_last, the other tensors are empty."""
-    from .ops import TCN_SALT
     from .tcn_plan import train_tables
     lib = load_library()
     x = _c(x)
@@ -1009,15 +980,11 @@ def _tcn_predictor_bwd(ctx, grads):
     if dh is None:
         return (None,) * 9
     n = ctx.n
-    sv = ctx.saved_tensors
-    x, conv_w, ln_w = sv[0], list(sv[1:1 + n]), list(sv[1 + n:1 + 2 * n])
-    rest = sv[1 + 2 * n:]
-    s, xhat, rstd, outs = list(rest[:n]), list(rest[n:2 * n]), list(rest[2 * n:3 * n]), list(rest[3 * n:])
+    (x,), conv_w, ln_w, s, xhat, rstd, outs = _split(ctx.saved_tensors, 1, n, n, n, n, n, n // 2)
     need_dx = ctx.needs_input_grad[0]
     out = torch.ops.leakgnn.tcn_predictor_backward(dh.contiguous(), x, conv_w, ln_w, s, xhat, rstd, outs, ctx.p, need_dx)
-    g = out[1:]
-    return (out[0] if need_dx else None, list(g[:n]), list(g[n:2 * n]), list(g[2 * n:3 * n]), list(g[3 * n:]),
-            None, None, None, None)
+    (dx,), *dws = _split(out, 1, n, n, n, n)
+    return (dx if need_dx else None, *dws, None, None, None, None)
 
 
 tcn_predictor.register_autograd(_tcn_predictor_bwd, setup_context=_tcn_predictor_setup)

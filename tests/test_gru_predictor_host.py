@@ -67,13 +67,30 @@ def test_op_shape_checks():
     x = torch.zeros(2, 5, I)
     good = dict(w_ih=[torch.zeros(3 * H, I), torch.zeros(3 * H, H)], w_hh=[torch.zeros(3 * H, H)] * 2,
                 b_ih=[torch.zeros(3 * H)] * 2, b_hh=[torch.zeros(3 * H)] * 2)
-    assert library._predictor_dims(x, **good) == (2, 5, I, H, 2)
-    for key, bad in (("w_ih", [torch.zeros(3 * H, I), torch.zeros(3 * H, I)]), ("w_hh", [torch.zeros(3 * H, H)]),
-                     ("b_hh", [torch.zeros(3 * H), torch.zeros(H)]), ("w_ih", [torch.zeros(2 * H, I), torch.zeros(3 * H, H)])):
-        with pytest.raises(ValueError):
-            library._predictor_dims(x, **{**good, key: bad})
+    bads = (("w_ih", [torch.zeros(3 * H, I), torch.zeros(3 * H, I)]), ("w_hh", [torch.zeros(3 * H, H)]),
+            ("b_hh", [torch.zeros(3 * H), torch.zeros(H)]), ("w_ih", [torch.zeros(2 * H, I), torch.zeros(3 * H, H)]))
+    # the one validator under gru_predictor (dense x) and gru_stack (residual, I from w_ih[0])
+    for op, inp, dense in (("gru_predictor", x, True), ("gru_stack", torch.zeros(2, 5, 7), False)):
+        assert library._gru_dims(op, inp, dense, **good) == (I, H, 2)
+        assert library._gru_dims(op, inp, dense, good["w_ih"], good["w_hh"]) == (I, H, 2)  # the backward ops: no biases
+        for key, bad in bads:
+            with pytest.raises(ValueError, match=f"^{op}: "):
+                library._gru_dims(op, inp, dense, **{**good, key: bad})
+        with pytest.raises(ValueError, match=f"^{op}: "):
+            library._gru_dims(op, torch.zeros(2, 5), dense, **good)
+        with pytest.raises(ValueError, match=f"^{op}: dropout p"):
+            library._gru_dims(op, inp, dense, **good, p=1.0)
+    with pytest.raises(ValueError, match="I, H in 1..1024"):
+        library._gru_dims("gru_predictor", torch.zeros(2, 5, 1025), True, [torch.zeros(3 * H, 1025)], [torch.zeros(3 * H, H)])
+
+
+def test_split_runs():
+    from models import library
+    ts = [torch.zeros(i) for i in range(6)]
+    (a,), b, c = library._split(ts, 1, 2, 3)
+    assert a is ts[0] and b == ts[1:3] and c == ts[3:] and library._split(tuple(ts), 6, 0) == [ts, []]
     with pytest.raises(ValueError):
-        library._predictor_dims(torch.zeros(2, 5), **good)
+        library._split(ts, 2, 3)
 
 
 def test_fast_path_eligibility():
