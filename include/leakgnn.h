@@ -143,7 +143,14 @@ const char* lg_strerror(int code);
  *        over rows in row order.  counter: a device uint32, 0 between launches (the launch
  *        resets it); one per stream that may run this concurrently.
  *   bwd: dlogits[b][c] = grad_loss[0] / n * (exp(x - lse[b]) - [c == target[b]]), 0 for
- *        ignored rows (row stride ldd).  Three launches for what torch runs as six. */
+ *        ignored rows (row stride ldd).  Three launches for what torch runs as six.
+ *   lse[b] rounds at the size of the logits.  Rows with |lse[b]| >= 32 therefore take the row
+ *   loss as (max - x[target]) + log(sum) and the softmax as exp(x - max) / sum, the backward
+ *   finding max and sum again; below 32 the rounding is under 1e-6 and the forms above hold.
+ *   A target outside [0, C) other than ignore_index (torch raises) gives a NaN loss, reads
+ *   nothing out of range, and its dlogits row is the softmax with no one-hot term.  B == 0:
+ *   loss = NaN, nothing else written.  Tested against torch's fp64 cross_entropy in
+ *   tests/test_gpu_step_tail.py. */
 int lg_cross_entropy_fwd(const float* logits, const int64_t* target, int64_t B, int64_t C, int64_t ldx,
                          int64_t ignore_index, float* loss, float* lse, float* rowloss, unsigned* counter,
                          lg_stream_t stream);
@@ -166,7 +173,12 @@ int lg_cross_entropy_bwd(const float* logits, const int64_t* target, const float
  *   workspace: lg_clip_adamw_workspace_bytes(sizes, T) bytes (ABI 25: one fp64 partial sum of
  *           squares per slice; each workgroup reads and writes only its own gradient slice).
  * The norm is summed in fp64 in a fixed order (deterministic; the one- and two-launch forms
- * give identical bits). */
+ * give identical bits).  Non-finite gradients behave as torch's pair does (error_if_nonfinite
+ * False): a NaN norm gives a NaN clip coefficient, so every clipped gradient and parameter
+ * becomes NaN; an infinite norm gives coefficient 0.  eps == 0 with a gradient entry of
+ * exactly 0 in a fresh state is 0 / 0: that parameter entry becomes NaN, as in torch's AdamW.
+ * T == 0 is legal (the step counter still advances).  Every mode is tested against an fp64
+ * AdamW in tests/test_gpu_step_tail.py. */
 int64_t lg_clip_adamw_workspace_bytes(const int64_t* sizes, int T);
 int lg_clip_adamw(const int64_t* table, const int64_t* sizes, int T, float* step, float lr, float beta1,
                   float beta2, float eps, float weight_decay, float max_norm, float* norm_out, void* workspace, int64_t ws_bytes,

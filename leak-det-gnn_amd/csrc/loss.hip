@@ -16,6 +16,12 @@
 //             100 MB of stores, made the launch 12 us for 0.8 MB of logits; round 4 ran the
 //             mean as a second, single-wave launch, ~5 us in the step.)
 //   backward: dx[b][c] = g / n * (exp(x - lse[b]) - [c == target[b]])   (0 for ignored rows)
+// lse[b] is one float, so it rounds at the size of the logits: by at most 2^-20 = 9.5e-7 below
+// kCeLseFine = 32 (the absolute error it leaves in lse - x[target] and the relative error in
+// exp(x - lse): under 1e-6), by 4.9e-4 at logits near 1e4, where it was 50 x the loss's
+// bar (tests/test_gpu_step_tail.py).  Rows whose |lse| is not below kCeLseFine therefore take
+// the row loss as (max - x[target]) + log(sum) and the softmax as exp(x - max) / sum, the
+// backward finding the row's max and sum again; all other rows keep the one-pass forms above.
 #include <algorithm>
 #include "common.h"
 
@@ -24,6 +30,7 @@ namespace {
 constexpr int kCeWaves = 4;
 constexpr int kCeThreads = 64 * kCeWaves;
 constexpr int kCePer = 16;  // row elements per lane held in registers (C <= 1024)
+constexpr float kCeLseFine = 32.f;  // below it lse[b]'s rounding is under 1e-6 (header)
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
@@ -81,12 +88,14 @@ k_ce_fwd(const float* __restrict__ x, const int64_t* __restrict__ target, int64_
             for (int64_t c = lane; c < C; c += 64) s += expf(row[c] - m);
         }
         s = wave_sum(s);
-        const float l = m + logf(s);
+        const float ls = logf(s);
+        const float l = m + ls;
         if (lane == 0) {
             const int64_t t = target[b];
             lse[b] = l;
             // a target outside [0, C) (torch raises) poisons the loss with NaN, never reads out of bounds
-            const float rl = t == ignore ? 0.f : (t >= 0 && t < C ? l - row[t] : __builtin_nanf(""));
+            float rl = t == ignore ? 0.f : __builtin_nanf("");
+            if (t >= 0 && t < C && t != ignore) rl = fabsf(l) < kCeLseFine ? l - row[t] : (m - row[t]) + ls;
             __hip_atomic_store(rowloss + b, rl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
@@ -120,6 +129,7 @@ k_ce_bwd(const float* __restrict__ x, const int64_t* __restrict__ target, const 
         const int64_t t = target[b];
         const float l = lse[b];
         const float gi = t == ignore ? 0.f : g;
+        const bool fine = fabsf(l) < kCeLseFine;  // the same in every lane
         if (C <= 64 * kCePer) {
             float v[kCePer];
 #pragma unroll
@@ -127,13 +137,38 @@ k_ce_bwd(const float* __restrict__ x, const int64_t* __restrict__ target, const 
                 const int64_t c = lane + 64 * k;
                 v[k] = c < C ? row[c] : 0.f;
             }
+            if (fine) {
 #pragma unroll
-            for (int k = 0; k < kCePer; ++k) {
-                const int64_t c = lane + 64 * k;
-                if (c < C) drow[c] = gi * (expf(v[k] - l) - (c == t ? 1.f : 0.f));
+                for (int k = 0; k < kCePer; ++k) {
+                    const int64_t c = lane + 64 * k;
+                    if (c < C) drow[c] = gi * (expf(v[k] - l) - (c == t ? 1.f : 0.f));
+                }
+            } else {
+                float m = -__builtin_huge_valf(), s = 0.f;
+#pragma unroll
+                for (int k = 0; k < kCePer; ++k) m = lane + 64 * k < C ? fmaxf(m, v[k]) : m;
+                m = wave_max(m);
+#pragma unroll
+                for (int k = 0; k < kCePer; ++k) {
+                    v[k] = lane + 64 * k < C ? expf(v[k] - m) : 0.f;
+                    s += v[k];
+                }
+                const float rs = 1.f / wave_sum(s);
+#pragma unroll
+                for (int k = 0; k < kCePer; ++k) {
+                    const int64_t c = lane + 64 * k;
+                    if (c < C) drow[c] = gi * (v[k] * rs - (c == t ? 1.f : 0.f));
+                }
             }
-        } else {
+        } else if (fine) {
             for (int64_t c = lane; c < C; c += 64) drow[c] = gi * (expf(row[c] - l) - (c == t ? 1.f : 0.f));
+        } else {
+            float m = -__builtin_huge_valf(), s = 0.f;
+            for (int64_t c = lane; c < C; c += 64) m = fmaxf(m, row[c]);
+            m = wave_max(m);
+            for (int64_t c = lane; c < C; c += 64) s += expf(row[c] - m);
+            const float rs = 1.f / wave_sum(s);
+            for (int64_t c = lane; c < C; c += 64) drow[c] = gi * (expf(row[c] - m) * rs - (c == t ? 1.f : 0.f));
         }
     }
 }
@@ -150,7 +185,6 @@ extern "C" int lg_cross_entropy_fwd(const float* logits, const int64_t* target, 
                                                                                                           : LG_EHIP;
     }
     if (!logits || !target || !lse || !rowloss) return LG_EINVAL;
-    // at most one workgroup per CU: the sc1 hand-off above was measured in that configuration
     // at most one workgroup per CU: every workgroup of the launch is co-resident, so the last
     // ticket is taken only after every workgroup's row losses have left (the fence-free
     // hand-off above was validated at this grid; larger B loops inside the workgroups,

@@ -10,7 +10,8 @@
 //      count is <= the CU count, so every slice is resident and the wait ends;
 //   3. every workgroup sums the G partials in slice order (the same bits everywhere), clips
 //      and updates its slice:
-//     g     = grad * min(1, max_norm / (||grad||_2 + 1e-6))     (written back, as torch does)
+//     g     = grad * min(1, max_norm / (||grad||_2 + 1e-6))     (written back, as torch does;
+//                                                                 a NaN norm gives NaN, as torch's clamp)
 //     p    *= 1 - lr * weight_decay                              (decoupled decay)
 //     m     = beta1 m + (1 - beta1) g,   v = beta2 v + (1 - beta2) g^2
 //     p    -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
@@ -108,6 +109,8 @@ k_adam(AdamTensors a, float* __restrict__ step, float lr, float beta1, float bet
     uint32_t* ctr = reinterpret_cast<uint32_t*>(step + 1);
     // the committed step count, read before this workgroup's arrival / ticket (below)
     if (tid == 0) tsh = __hip_atomic_load(step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1.0f;
+    // the other two modes reach their read of tsh through opt_block_sum's barriers; this one has none
+    if (MODE == kAdamNoNorm) __syncthreads();
     const int64_t e = static_cast<int64_t>(blockIdx.x) * kOptChunk + tid;
     const int t = opt_tensor_of(a, e);
     const bool live = t < a.T;
@@ -168,8 +171,9 @@ k_adam(AdamTensors a, float* __restrict__ step, float lr, float beta1, float bet
         }
     }
     if (!live) return;
-    const float coef = max_norm > 0.f ? static_cast<float>(fmin(1.0, static_cast<double>(max_norm) / (norm + 1e-6)))
-                                      : 1.0f;
+    // min(1, ratio) as torch's clamp(max=1): a NaN norm gives a NaN coefficient (fmin would drop it)
+    const double ratio = static_cast<double>(max_norm) / (norm + 1e-6);
+    const float coef = max_norm > 0.f ? static_cast<float>(ratio >= 1.0 ? 1.0 : ratio) : 1.0f;
     const float bc1 = 1.0f - powf(beta1, t1), bc2 = 1.0f - powf(beta2, t1);
     const float step_size = lr / bc1, bc2s = sqrtf(bc2), decay = 1.0f - lr * wd;
     if (max_norm > 0.f) {
