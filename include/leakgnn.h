@@ -796,6 +796,14 @@ int lg_gru_win_fwd(const float* gi, const float* w_hh, const float* b_hh, float*
  *        writes them from h_last (W = proj_w [H][H + 1], bias = node_bias, dropout stream =
  *        (seed, salt)), except that the sensor nodes' words of x0bits are 0 (no reader:
  *        lg_gcn_fwd_nm_x0 / lg_gcn_bwd_nm_x0 take those rows from xs0).  One launch.
+ *        h_seq / gates hold lg_gru_fwd's values but are PRIVATE to this pair (written here, read
+ *        by lg_gru_node_init_bwd alone), in the order the kernels' lanes hold them, so that every
+ *        wave store and load moves 1 KB contiguous.  Sequences come in blocks of 16, B * S rounded
+ *        up: nb16 = ceil(B * S / 16), NU = H / 16,
+ *          h_seq [L][nb16][NU][64][4]        gates [L][nb16][4: r, z, n, hn][NU][64][4]
+ *        i.e. 16 * nb16 rows a step instead of B * S; element (t, seq, unit i) is at block
+ *        seq >> 4, u = i >> 4, lane 16 * ((i >> 2) & 3) + (seq & 15), reg i & 3.  The entries of
+ *        the last block's sequences >= B * S are written as 0.
  *   bwd: lg_gru_bwd without dx, its dh_last formed in the launch from the node init's
  *        pre-activation gradient, as lg_sensor_proj_bwd does: dx0 is node-major [N][B][H] (the
  *        sensor nodes' rows: lg_gcn_bwd_nm_x0 with LG_F_DX_SENSOR_ROWS), live [S] (may be NULL);

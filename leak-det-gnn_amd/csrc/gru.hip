@@ -36,6 +36,9 @@
 // every later kernel of the step ran faster (trunk backward 48.2 -> 45.5 us, GRU backward 101.5
 // -> 96.7, EdgeHead 56.1 / 130.0 -> 53.2 / 127.2) for 5 us more in this kernel; step sum 561 ->
 // 552 us (r06t, same box).  nt alone took this kernel to 124 us (64-byte row pieces per store).
+// Re-measured with the fused pair's 1 KB lane-order stores (BLK; ms per step, same box, three
+// alternations): 18 0.5217 / 0.5251 / 0.5219, sc1 alone 0.5316 / 0.5319 / 0.5263, nt alone
+// 0.5221 / 0.5239 / 0.5267 (level with 18 now): 18 stays.
 #define LG_GRU_AUX 18
 #endif
 #ifndef LG_GRU_LAUX
@@ -201,7 +204,17 @@ __device__ __forceinline__ void gru_ni_bits(const GruNi& ni, uint32_t blk, uint3
 }
 
 // gates (optional) [L][Nseq][4][H]: r, z, n, W_hn h_{t-1} + b_hn
-template <int H, bool UT, bool SAVE, bool NI = false>
+// BLK (the fused pair lg_gru_node_init_fwd / _bwd, whose saved steps nobody else reads): each
+// wave's f32x4 per lane is saved in lane order, so one store instruction writes one contiguous
+// 1 KB instead of a 64-byte piece of 16 rows, and k_gru_bwd2's wave (w, sh) of workgroup m, which
+// holds the same units of the same sequences in the same lanes as wave u = w of block 2m + sh
+// here, loads it back the same way.  With nb16 = ceil(Nseq / 16) blocks a step:
+//   hs    [L][nb16][NU][64 lanes][4]        gates [L][nb16][4 planes][NU][64 lanes][4]
+// element (t, seq, unit i): block seq >> 4, u = i >> 4, lane 16 * ((i >> 2) & 3) + (seq & 15),
+// reg i & 3.  A padded sequence's lanes are stored as 0 (the row layout leaves them out and the
+// backward reads 0 past the descriptor's end).  The descriptor's base is scalar (step, block,
+// plane, wave), the lane's offset lane * 16 is the only vector one.
+template <int H, bool UT, bool SAVE, bool NI = false, bool BLK = false>
 __global__ void __launch_bounds__(12 * H) __attribute__((amdgpu_waves_per_eu(6, 8)))  // 2 workgroups / CU
 k_gru_fwd(const float* __restrict__ resid, const float* __restrict__ tfeat, const float* __restrict__ Wih,
           const float* __restrict__ Whh, const float* __restrict__ bih, const float* __restrict__ bhh,
@@ -223,6 +236,16 @@ k_gru_fwd(const float* __restrict__ resid, const float* __restrict__ tfeat, cons
     const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
     const uint32_t seq0 = blockIdx.x * TS, seq = seq0 + j;
     const bool valid = seq < Nseq;
+    // BLK: 16 B of plane `pl` (gates: r, z, n, hn; hs: 0) of step t.  The descriptor is the wave's
+    // own 1 KB of the block (scalar arithmetic), the offset operand stays 0: a 16-byte buffer store
+    // with an SGPR offset has its data registers reused too early by this compiler (see
+    // lg_store_guard, gcn_nm.hip; here the hn plane went out overwritten by the h split)
+    [[maybe_unused]] const int64_t nb16 = (static_cast<int64_t>(Nseq) + TS - 1) / TS;
+    [[maybe_unused]] auto st_blk = [&](float* p, int planes, int pl, int t, f32x4 v) {
+        const int64_t wv = ((static_cast<int64_t>(t) * nb16 + blockIdx.x) * planes + pl) * NU + u;
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(lg_u32x4, valid ? v : zero4()),
+                                               lg_act_rsrc(p + wv * 256, 256), lane * 16, 0, LG_GRU_AUX);
+    };
 
     // the h / gate stores go through buffer descriptors over one step's rows (base advanced per
     // step in SGPRs, 32-bit offsets within the step: Nseq * 4H * 4 bytes < 2^31, checked on the
@@ -321,7 +344,8 @@ k_gru_fwd(const float* __restrict__ resid, const float* __restrict__ tfeat, cons
                 grz[g][u][lane] = sg;
                 // the r / z waves store their own gate (the n waves' phase between the barriers is
                 // the step's critical path; it keeps the n, W_hn h + b_hn and h stores)
-                if (SAVE && valid)
+                if constexpr (SAVE && BLK) st_blk(gates, 4, g, t, sg);
+                else if (SAVE && valid)
                     st4_act<LG_GRU_AUX>(lg_act_rsrc(gates + static_cast<int64_t>(t) * Nseq * 4 * H, static_cast<int64_t>(Nseq) * 4 * H),
                             seq * 4 * H + g * H + 16 * u + 4 * q, sg);
             }
@@ -335,7 +359,13 @@ k_gru_fwd(const float* __restrict__ resid, const float* __restrict__ tfeat, cons
                     n[reg] = gru_tanh(a0[reg] + r[reg] * hp[reg]);
                     hcur[reg] = (1.f - z[reg]) * n[reg] + z[reg] * hcur[reg];
                 }
-                if (valid) {
+                if constexpr (BLK) {
+                    if (hs) st_blk(hs, 1, 0, t, hcur);
+                    if constexpr (SAVE) {  // r, z: stored by their waves
+                        st_blk(gates, 4, 2, t, n);
+                        st_blk(gates, 4, 3, t, hp);
+                    }
+                } else if (valid) {
                     const int64_t rw = static_cast<int64_t>(t) * Nseq + seq;
                     (void)rw;
                     if (hs)
@@ -736,7 +766,8 @@ struct GruNiB {
     uint32_t B;
 };
 
-template <int H, bool UT, bool F16, bool DEFER, bool NI = false>
+// BLK: hs / gates in the lane-order layout k_gru_fwd<.., BLK> saved them in (see there).
+template <int H, bool UT, bool F16, bool DEFER, bool NI = false, bool BLK = false>
 __global__ void __launch_bounds__(GB2<H>::NTH)
 k_gru_bwd2(const float* __restrict__ resid, const float* __restrict__ tfeat, const float* __restrict__ Whh,
            const float* __restrict__ hs, const float* __restrict__ gates, const float* __restrict__ dhL,
@@ -838,8 +869,27 @@ k_gru_bwd2(const float* __restrict__ resid, const float* __restrict__ tfeat, con
     // gates / h through buffer loads: the base (step t, the workgroup's first sequence) is
     // scalar, the lane's offset fixed, and a padded sequence's rows lie past the resource's
     // end (read as 0)
+    // BLK: the wave's half of the workgroup is forward block 2 * blockIdx.x + sh, its lanes the
+    // forward wave's; the descriptor covers that block's planes of step t (base scalar, the plane /
+    // wave offset scalar, lane * 16 the only vector offset: 1 KB contiguous a load), and has no
+    // records where the forward had no such block (odd nb16: read as 0, as a padded sequence's)
     const int nsq = static_cast<int>(min(Nseq - seq0, static_cast<uint32_t>(TS2)));
+    [[maybe_unused]] const int64_t nb16 = (static_cast<int64_t>(Nseq) + 15) / 16;
+    [[maybe_unused]] const int64_t fblk = 2 * static_cast<int64_t>(blockIdx.x) + sh;
+    [[maybe_unused]] auto ld_blk = [&](const float* p, int planes, int pl, int t) -> f32x4 {
+        const int64_t blkf = static_cast<int64_t>(planes) * G::NW * 256;  // floats of one block's planes
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<float*>(p + (static_cast<int64_t>(max(t, 0)) * nb16 + fblk) * blkf), static_cast<short>(0),
+            fblk < nb16 ? static_cast<int>(blkf * 4) : 0, 0x00020000);
+        return __builtin_bit_cast(
+            f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, (pl * G::NW + w) * 1024, LG_GRU_LAUX));
+    };
     auto load_g = [&](int t, f32x4 (&g)[4]) {
+        if constexpr (BLK) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g[k] = ld_blk(gates, 4, k, t);
+            return;
+        }
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<float*>(gates + (static_cast<int64_t>(max(t, 0)) * Nseq + seq0) * 4 * H), static_cast<short>(0),
             nsq * 4 * H * 4, 0x00020000);
@@ -848,6 +898,7 @@ k_gru_bwd2(const float* __restrict__ resid, const float* __restrict__ tfeat, con
             g[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (sl * 4 * H + u0 + k * H) * 4, 0, LG_GRU_LAUX));
     };
     auto load_h = [&](int t) -> f32x4 {  // h_t of this lane's units (h_0 for t < 0: masked at use)
+        if constexpr (BLK) return ld_blk(hs, 1, 0, t);
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<float*>(hs + (static_cast<int64_t>(max(t, 0)) * Nseq + seq0) * H), static_cast<short>(0),
             nsq * H * 4, 0x00020000);
@@ -1208,7 +1259,11 @@ k_gru_bwd2(const float* __restrict__ resid, const float* __restrict__ tfeat, con
                 const uint32_t b = lg_div(sq, fdS), sl2 = sq - b * fdS.d;
                 v = ld4(ni.dx0 + (static_cast<int64_t>(ni.sidx[sl2]) * ni.B + b) * D + c4);
                 if (ni.live) v = v * ni.live[sl2];
-                hv = ld4(hs + (static_cast<int64_t>(L - 1) * Nseq + sq) * H + c4);
+                if constexpr (BLK)  // units c4 .. c4 + 3 of sq: block sq >> 4, wave c4 >> 4, lane (q, j)
+                    hv = ld4(hs + ((static_cast<int64_t>(L - 1) * nb16 + (sq >> 4)) * G::NW + (c4 >> 4)) * 256 +
+                             4 * (16 * ((c4 >> 2) & 3) + (sq & 15)));
+                else
+                    hv = ld4(hs + (static_cast<int64_t>(L - 1) * Nseq + sq) * H + c4);
             }
             st4(dpl + rr * DP + c4, v);
             st4(hx + rr * HP + c4, hv);
@@ -2020,6 +2075,13 @@ extern "C" int lg_gru_bwd(const float* residual, const float* tfeat, const float
 }
 
 // ------------------------------------------------------------------ GRU + node init, fused
+// h_seq / gates are private to the pair, in the lane-order layout (k_gru_fwd, BLK)
+#ifndef LG_GRU_NI_BLK
+#define LG_GRU_NI_BLK 1  // lab: 0 = the row layout of lg_gru_fwd
+#endif
+namespace {
+constexpr bool kGruNiBlk = LG_GRU_NI_BLK != 0;
+}
 extern "C" int lg_gru_node_init_fwd(const float* residual, const float* tfeat, const float* w_ih, const float* w_hh,
                                     const float* b_ih, const float* b_hh, float* h_seq, float* gates, float* h_last,
                                     const int32_t* sensor_slot, const int64_t* sensor_idx, const float* proj_w,
@@ -2031,7 +2093,7 @@ extern "C" int lg_gru_node_init_fwd(const float* residual, const float* tfeat, c
     if (!residual || !w_ih || !w_hh || !b_ih || !b_hh || !h_last || (I == 10 && !tfeat)) return LG_EINVAL;
     if (!sensor_slot || !sensor_idx || !proj_w || !node_bias || !xs0 || !x0bits) return LG_EINVAL;
     if (gates && !h_seq) return LG_EINVAL;
-    if (!fwd_rows_ok(B, S, H)) return LG_EUNSUPPORTED;
+    if (!fwd_rows_ok((B * S + TS - 1) / TS * TS, 1, H)) return LG_EUNSUPPORTED;  // the saved rows: whole blocks
     const bool drop = (flags & LG_F_DROPOUT) != 0;
     if (drop && !(dropout_p >= 0.f && dropout_p < 1.f)) return LG_EINVAL;
     if (B == 0) return LG_OK;
@@ -2050,7 +2112,7 @@ extern "C" int lg_gru_node_init_fwd(const float* residual, const float* tfeat, c
                    lg_make_fastdiv(static_cast<uint32_t>(ngroups)), drop ? 1 : 0, dropout_p,
                    drop ? 1.0f / (1.0f - dropout_p) : 1.0f, seed, salt, static_cast<uint32_t>(nseqblk)};
 #define LG_GRU_NI(HH, UT, SV)                                                                                     \
-    lg_launch(k_gru_fwd<HH, UT, SV, true>, grid, 12 * HH, 0, s, residual, tfeat, w_ih, w_hh, b_ih, b_hh, h_seq, gates, \
+    lg_launch(k_gru_fwd<HH, UT, SV, true, kGruNiBlk>, grid, 12 * HH, 0, s, residual, tfeat, w_ih, w_hh, b_ih, b_hh, h_seq, gates, \
               h_last, Nseq, static_cast<int>(L), static_cast<int>(S), fdS, ni)
     const bool ut = I == 10, save = gates != nullptr;
     if (H == 64) {
@@ -2100,7 +2162,7 @@ extern "C" int lg_gru_node_init_bwd(const float* residual, const float* tfeat, c
         const lg_fastdiv fdS = lg_make_fastdiv(static_cast<uint32_t>(S));
         const GruNiB ni{dx0, sensor_idx, live, proj_w, dbias_in, static_cast<uint32_t>(B)};
 #define LG_GRU_NIB(HH, UT)                                                                                        \
-    lg_launch(k_gru_bwd2<HH, UT, true, true, true>, static_cast<unsigned>(nb), GB2<HH>::NTH, 0, s, residual, tfeat,   \
+    lg_launch(k_gru_bwd2<HH, UT, true, true, true, kGruNiBlk>, static_cast<unsigned>(nb), GB2<HH>::NTH, 0, s, residual, tfeat,   \
               w_hh, h_seq, gates, nullptr, slab, Nseq, static_cast<int>(L), static_cast<int>(S), fdS, ni)
         if (H == 64) {
             if (I == 10) LG_GRU_NIB(64, true); else LG_GRU_NIB(64, false);

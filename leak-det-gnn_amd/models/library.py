@@ -1304,6 +1304,12 @@ def encoder_trunk_supported(B: int, N: int, H: int, D: int, L: int, node_major: 
             and _compress_x0(torch.empty(0), node_major, L))
 
 
+def _gru_ni_rows(nseq: int) -> int:
+    """Rows per step of lg_gru_node_init_fwd's h_seq / gates: the sequences rounded up to whole
+    16-sequence blocks (include/leakgnn.h)."""
+    return 16 * ((nseq + 15) // 16)
+
+
 @torch.library.custom_op(f"{NS}::encoder_trunk", mutates_args=(), device_types="cuda")
 def encoder_trunk(residual: Tensor, tfeat: Optional[Tensor], w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor,
                   proj_weight: Tensor, node_bias: Tensor, weights: List[Tensor], biases: List[Tensor],
@@ -1338,8 +1344,10 @@ def encoder_trunk(residual: Tensor, tfeat: Optional[Tensor], w_ih: Tensor, w_hh:
     seed_v, sbit = _seed_args(seed) if drop else (0, 0)
     dflag = nat.LG_F_DROPOUT if drop else 0
     nmask = N * ((B + 15) // 16) * 64
-    h_seq = torch.empty(Lw, B * S, H, device=dev) if save else torch.empty(0, device=dev)
-    gates = torch.empty(Lw, B * S, 4, H, device=dev) if save else torch.empty(0, device=dev)
+    # the fused pair's saved steps: private to lg_gru_node_init_fwd / _bwd, in 16-sequence blocks
+    rows = _gru_ni_rows(B * S)
+    h_seq = torch.empty(Lw, rows, H, device=dev) if save else torch.empty(0, device=dev)
+    gates = torch.empty(Lw, rows, 4, H, device=dev) if save else torch.empty(0, device=dev)
     h_last = torch.empty(B, S, H, device=dev)
     xs0 = torch.empty((S, B, D), device=dev, dtype=torch.float32)
     x0bits = torch.empty(nmask, device=dev, dtype=torch.int16)
@@ -1376,8 +1384,9 @@ def _(residual, tfeat, w_ih, w_hh, b_ih, b_hh, proj_weight, node_bias, weights, 
     D = proj_weight.shape[0]
     N = sensor_slot.shape[0]
     nmask = N * ((B + 15) // 16) * 64
-    h_seq = residual.new_empty(Lw, B * S, H) if save else residual.new_empty(0)
-    gates = residual.new_empty(Lw, B * S, 4, H) if save else residual.new_empty(0)
+    rows = _gru_ni_rows(B * S)
+    h_seq = residual.new_empty(Lw, rows, H) if save else residual.new_empty(0)
+    gates = residual.new_empty(Lw, rows, 4, H) if save else residual.new_empty(0)
     return ([residual.new_empty(N, B, D) for _ in weights] + [residual.new_empty((nmask,), dtype=torch.int16),
             residual.new_empty(S, B, D), residual.new_empty((nmask,), dtype=torch.int16), h_seq, gates])
 

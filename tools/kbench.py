@@ -1,7 +1,7 @@
 """Kernel micro-benchmark (GPU): times individual libleakgnn kernels in isolation with
 HIP events on the launch stream.  Used for tuning and under rocprofv3 --pmc.
 
-  python tools/kbench.py [--which gcn_fwd,gcn_bwd,spmm,edge_fwd,edge_bwd,gru_fwd,gru_bwd,gru_stack,gru_predictor,tcn,tcn_train] [--B 256] [--iters 50]
+  python tools/kbench.py [--which gcn_fwd,gcn_bwd,spmm,edge_fwd,edge_bwd,gru_fwd,gru_bwd,gru_ni_fwd,gru_ni_bwd,gru_stack,gru_predictor,tcn,tcn_train] [--B 256] [--iters 50]
 """
 import argparse
 import ctypes
@@ -612,6 +612,41 @@ def main():
             res["gru_bwd"] = {"us": t, "TFLOPs": 2 * flops / t / 1e6}
             if args.stamps and hasattr(lib, "lg_lab_gru_stamps"):
                 res["stamps_gru_bwd"] = gru_stamps_summary(lib, f)
+    if "gru_ni_fwd" in which or "gru_ni_bwd" in which:
+        # the fused pair of the step (lg_gru_node_init_fwd / _bwd: the GRU with the node init in its
+        # epilogue, the projection's backward around the GRU backward), saved steps in their own layout
+        S, L = 29, 36
+        r = torch.randn(B, L, S, device=dev)
+        tf = torch.randn(B, L, 9, device=dev)
+        wih = torch.randn(192, 10, device=dev) / 4
+        whh = torch.randn(192, 64, device=dev) / 8
+        bih, bhh = torch.randn(192, device=dev) / 4, torch.randn(192, device=dev) / 4
+        rows = 16 * ((B * S + 15) // 16)
+        hs = torch.empty(L, rows, 64, device=dev)
+        gt = torch.empty(L, rows, 4, 64, device=dev)
+        hl = torch.empty(B * S, 64, device=dev)
+        slot = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        slot[:S] = torch.arange(S, dtype=torch.int32, device=dev)
+        sidx = torch.arange(S, dtype=torch.int64, device=dev)
+        Wp = torch.randn(D, D + 1, device=dev) / 8
+        xs0 = torch.empty(S, B, D, device=dev)
+        x0b = torch.empty(N * ((B + 15) // 16) * 64, device=dev, dtype=torch.int16)
+        f = lambda: check(lib.lg_gru_node_init_fwd(ptr(r), ptr(tf), ptr(wih), ptr(whh), ptr(bih), ptr(bhh), ptr(hs),
+                                                   ptr(gt), ptr(hl), ptr(slot), ptr(sidx), ptr(Wp), ptr(bias), ptr(xs0),
+                                                   ptr(x0b), B, L, S, 10, 64, N, nat.LG_F_DROPOUT, 0.1, 123, 0, cs()),
+                          "gru ni fwd")
+        t = timeit(f, args.iters)
+        saved = 4 * L * rows * 5 * 64
+        res["gru_ni_fwd"] = {"us": t, "saved_GBps": saved / t / 1e3}
+        if "gru_ni_bwd" in which:
+            dx0 = torch.randn(N, B, D, device=dev)
+            dws = [torch.empty_like(t) for t in (wih, whh, bih, bhh, Wp, bias)]
+            ws = torch.empty(int(lib.lg_gru_node_init_bwd_workspace_bytes(B, S, 10, 64)), device=dev, dtype=torch.uint8)
+            f = lambda: check(lib.lg_gru_node_init_bwd(ptr(r), ptr(tf), ptr(wih), ptr(whh), ptr(hs), ptr(gt), ptr(dx0),
+                                                       ptr(sidx), None, ptr(Wp), None, *(ptr(t) for t in dws), B, L, S,
+                                                       10, 64, N, ptr(ws), ws.numel(), cs()), "gru ni bwd")
+            t = timeit(f, args.iters)
+            res["gru_ni_bwd"] = {"us": t, "saved_GBps": saved / t / 1e3}
     if "gru_stack" in which:
         # the 2-layer sensor encoder (leakgnn::gru_stack) against (a) stock torch.nn.GRU(10, 64,
         # num_layers=2) in fp32 on the same device, its (B*S, L, 10) input prebuilt, and (b) the
