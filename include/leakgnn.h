@@ -879,6 +879,32 @@ int lg_tcn_conv_bwd(const float* dy, const float* s, const float* xhat, const fl
                     float* dbeta, int64_t nseg, int64_t rows_in, int64_t rows_res, int64_t rows_out, int64_t C,
                     void* workspace, int64_t ws_bytes, lg_stream_t stream);
 
+/* ---- Predictor training tail: head = nn.Linear(H, S) on h_last, then nn.MSELoss() ------
+ * (reference models/train_predictor.py: loss_fn(model(x, x_time), y); added to ABI 26 without a
+ * bump: additions only.)  All tensors fp32 and contiguous: h [B][H], weight [S][H], bias [S],
+ * target [B][S].
+ *   fwd: y_hat [B][S] = h weight^T + bias (saved for the backward), loss (device scalar) =
+ *        mean((y_hat - target)^2) over B * S elements, ONE launch: rowsq [B] scratch takes each
+ *        row's sum of squares, and the workgroup that finishes last sums the rows in row order
+ *        (fp64).  counter: as for the cross-entropy forward above (a device uint32, 0 between
+ *        launches, one per stream).  weight is staged in LDS when S * H <= 39,936 floats and its
+ *        address is 16-byte aligned, else read through L2.
+ *   bwd: with d = 2 grad_loss[0] / (B S) (y_hat - target): dh [B][H] = d weight, dweight [S][H]
+ *        = d^T h, dbias [S] = sum_b d.  One kernel launch writes dh and per-chunk partials of
+ *        [dweight | dbias] into the workspace; the fixed-order slab reduction (fp64, inside a
+ *        reduce batch when one is open) forms dweight and dbias.  No float atomics: equal bits on
+ *        every run.  Every output is overwritten.  ws_bytes below the workspace size is LG_EINVAL.
+ * Range: B >= 1, 1 <= H <= 1024, 1 <= S <= 1024, B * max(H, S) * 4 < 2^31; outside it, or with a
+ * null pointer, LG_EINVAL before any HIP call.  Tested against an fp64 CPU formula in
+ * tests/test_gpu_head_mse.py. */
+int lg_head_mse_fwd(const float* h, const float* weight, const float* bias, const float* target, int64_t B,
+                    int64_t H, int64_t S, float* y_hat, float* rowsq, float* loss, unsigned* counter,
+                    lg_stream_t stream);
+int64_t lg_head_mse_bwd_workspace_bytes(int64_t B, int64_t H, int64_t S);
+int lg_head_mse_bwd(const float* h, const float* weight, const float* target, const float* y_hat,
+                    const float* grad_loss, int64_t B, int64_t H, int64_t S, float* dh, float* dweight,
+                    float* dbias, void* workspace, int64_t ws_bytes, lg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

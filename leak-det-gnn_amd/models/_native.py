@@ -136,6 +136,10 @@ SIGNATURES = {
     "lg_tcn_conv_bwd_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "lg_tcn_conv_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _f32, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64,
                                _i64, _i64, _p, _i64, _p]),
+    # predictor head + MSE loss (added to ABI 26 without a bump: additions only)
+    "lg_head_mse_fwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
+    "lg_head_mse_bwd_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "lg_head_mse_bwd": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _i64, _p]),
 }
 
 _lib = None

@@ -804,12 +804,25 @@ _TCN_PACK_CACHE: "OrderedDict[int, tuple]" = OrderedDict()
 _TCN_PACK_MAX = 64
 
 
-def _tcn_packed(w: Tensor) -> Tuple[Tensor, Tensor]:
-    """(packed, transposed-packed) forms of a Conv1d weight (lg_tcn_pack_weight / _t), cached per
-    parameter (data_ptr, _version) as tcn_plan._packed_weights does: an in-place optimizer step bumps
-    the version and so invalidates the entry.  An entry keeps its weight tensor alive, so its address
-    cannot be handed to another tensor while the entry exists; the oldest entries are dropped."""
+def _tcn_packed(w: Tensor, transposed: bool) -> Tensor:
+    """The packed (forward) or transposed-packed (backward dx) form of a Conv1d weight
+    (lg_tcn_pack_weight / _t).  Eagerly both are made together and cached per parameter
+    (data_ptr, _version) as tcn_plan._packed_weights does: an in-place optimizer step bumps the
+    version and so invalidates the entry.  An entry keeps its weight tensor alive, so its address
+    cannot be handed to another tensor while the entry exists; the oldest entries are dropped.
+    While the stream is capturing, the cache is neither read nor written: the one pack launch the
+    caller needs is recorded in the graph, so every replay packs the weights it finds (a replayed
+    optimizer step changes them on the device without moving _version).  For the same reason
+    whoever replays such a graph calls invalidate_weight_packs() before the next eager call."""
     lib = load_library()
+    st = stream_of(w)
+    if torch.cuda.is_current_stream_capturing():
+        out = torch.empty(int(lib.lg_tcn_packed_weight_floats(128)), device=w.device)
+        if transposed:
+            check(lib.lg_tcn_pack_weight_t(ptr(w), ptr(out), 128, st), "lg_tcn_pack_weight_t")
+        else:
+            check(lib.lg_tcn_pack_weight(ptr(w), ptr(out), 128, st), "lg_tcn_pack_weight")
+        return out
     try:
         stamp = (w.data_ptr(), w._version)
     except RuntimeError:  # an inference tensor has no version counter: not cached
@@ -818,10 +831,9 @@ def _tcn_packed(w: Tensor) -> Tuple[Tensor, Tensor]:
         hit = _TCN_PACK_CACHE.get(stamp[0])
         if hit is not None and hit[0] == stamp[1]:
             _TCN_PACK_CACHE.move_to_end(stamp[0])
-            return hit[2], hit[3]
+            return hit[3] if transposed else hit[2]
     n = int(lib.lg_tcn_packed_weight_floats(128))
     pk, pkt = torch.empty(n, device=w.device), torch.empty(n, device=w.device)
-    st = stream_of(w)
     check(lib.lg_tcn_pack_weight(ptr(w), ptr(pk), 128, st), "lg_tcn_pack_weight")
     check(lib.lg_tcn_pack_weight_t(ptr(w), ptr(pkt), 128, st), "lg_tcn_pack_weight_t")
     if stamp is not None:
@@ -829,7 +841,17 @@ def _tcn_packed(w: Tensor) -> Tuple[Tensor, Tensor]:
         _TCN_PACK_CACHE.move_to_end(stamp[0])
         while len(_TCN_PACK_CACHE) > _TCN_PACK_MAX:
             _TCN_PACK_CACHE.popitem(last=False)
-    return pk, pkt
+    return pkt if transposed else pk
+
+
+def invalidate_weight_packs() -> None:
+    """Forget every cached packed weight (this module's and tcn_plan's).  A replayed HIP graph
+    that holds an optimizer step updates the weights without moving their _version, so the
+    captured predictor step calls this after each replay; the next eager call packs again.  A dict
+    clear and a counter bump, no device work."""
+    from . import tcn_plan
+    _TCN_PACK_CACHE.clear()
+    tcn_plan.invalidate_packed_weights()
 
 
 def _tcn_dims(x: Tensor, conv_w: List[Tensor], conv_b: List[Tensor], ln_w: List[Tensor], ln_b: List[Tensor]
@@ -879,7 +901,7 @@ def tcn_predictor(x: Tensor, conv_w: List[Tensor], conv_b: List[Tensor], ln_w: L
     with _timed("tcn_train_fwd", dev):
         for i in range(n):
             conv2 = i % 2 == 1
-            pk, _ = _tcn_packed(conv_w[i])
+            pk = _tcn_packed(conv_w[i], False)
             s = torch.empty(B * L, C, device=dev) if (save or p > 0.0 or not conv2) else None
             out = torch.empty(B * L, C, device=dev) if conv2 else None
             xh = torch.empty(B * L, C, device=dev) if save else None
@@ -941,7 +963,7 @@ def tcn_predictor_backward(dh: Tensor, x: Tensor, conv_w: List[Tensor], ln_w: Li
     dy = dy.view(B * L, C)
 
     def stage(i, dy_i, src, dres, dx):
-        _, pkt = _tcn_packed(conv_w[i])
+        pkt = _tcn_packed(conv_w[i], True)
         check(lib.lg_tcn_conv_bwd(ptr(dy_i), ptr(s[i]), ptr(xhat[i]), ptr(rstd[i]), ptr(src), ptr(dres), ptr(tabs[i]),
                                   ptr(tabs_t[i]), ptr(pkt), ptr(ln_w[i]), p, ptr(dz), ptr(dx), ptr(dws[i]), ptr(dbs[i]),
                                   ptr(dgs[i]), ptr(dbts[i]), B, L, L if dres is not None else 0, L, C, ptr(ws),

@@ -108,4 +108,9 @@ class ClipAdamW(torch.optim.Optimizer):
                       "lg_clip_adamw_seeds")
             else:
                 check(lib.lg_clip_adamw(*args, stream_of(params[0])), "lg_clip_adamw")
+            # the launch wrote the parameters through their addresses: move their version counters
+            # as an in-place torch op would, for whatever is cached per (data_ptr, _version)
+            # (library._tcn_packed).  Host only; a REPLAYED step moves nothing
+            # (library.invalidate_weight_packs).
+            torch.autograd.graph.increment_version(params)
         return loss

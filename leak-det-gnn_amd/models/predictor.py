@@ -89,7 +89,8 @@ class NormalPredictorTCN(nn.Module):
                 return False
         return True
 
-    def forward(self, x: torch.Tensor, x_time: torch.Tensor) -> torch.Tensor:
+    def features(self, x: torch.Tensor, x_time: torch.Tensor) -> torch.Tensor:
+        """(B, hidden): the last time step of the conv stack's output, everything before `head`."""
         xin = torch.cat([x, x_time], dim=-1)
         if TCN_TRAIN_HIP and xin.is_cuda and xin.dim() == 3 and xin.dtype == torch.float32:
             grad = torch.is_grad_enabled() and (xin.requires_grad or any(p.requires_grad for p in self.parameters()))
@@ -104,9 +105,12 @@ class NormalPredictorTCN(nn.Module):
                 out = torch.ops.leakgnn.tcn_predictor(h, [c.weight for c, _ in stages], [c.bias for c, _ in stages],
                                                       [n.weight for _, n in stages], [n.bias for _, n in stages],
                                                       float(self.tcn[0].norm1.eps), p, seed, grad)
-                return self.head(out[0])
+                return out[0]
         h = self.input_proj(xin.transpose(1, 2))                              # (B, hidden, L)
-        return self.head(self.tcn(h)[:, :, -1])                               # (B, S)
+        return self.tcn(h)[:, :, -1]
+
+    def forward(self, x: torch.Tensor, x_time: torch.Tensor) -> torch.Tensor:
+        return self.head(self.features(x, x_time))                            # (B, S)
 
 
 class NormalPredictorGRU(nn.Module):
@@ -119,7 +123,8 @@ class NormalPredictorGRU(nn.Module):
                           num_layers=num_layers, batch_first=True, dropout=dropout if num_layers > 1 else 0.0)
         self.head = nn.Linear(hidden_size, self.num_sensors)
 
-    def forward(self, x: torch.Tensor, x_time: torch.Tensor) -> torch.Tensor:
+    def features(self, x: torch.Tensor, x_time: torch.Tensor) -> torch.Tensor:
+        """(B, hidden): the top layer's last hidden state, everything before `head`."""
         xin = torch.cat([x, x_time], dim=-1)
         g = self.gru
         if xin.is_cuda and xin.dim() == 3 and g.batch_first and not g.bidirectional and g.bias and g.proj_size == 0:
@@ -129,6 +134,9 @@ class NormalPredictorGRU(nn.Module):
             p = float(g.dropout) if (self.training and nl > 1) else 0.0
             save = torch.is_grad_enabled() and (xin.requires_grad or any(w.requires_grad for wl in ws for w in wl))
             seed = library.seed_tensor(xin.device) if p > 0.0 else torch.zeros(1, dtype=torch.int64)
-            return self.head(torch.ops.leakgnn.gru_predictor(xin.float(), *ws, p, seed, save)[0])
+            return torch.ops.leakgnn.gru_predictor(xin.float(), *ws, p, seed, save)[0]
         out, _ = g(xin)
-        return self.head(out[:, -1, :])
+        return out[:, -1, :]
+
+    def forward(self, x: torch.Tensor, x_time: torch.Tensor) -> torch.Tensor:
+        return self.head(self.features(x, x_time))

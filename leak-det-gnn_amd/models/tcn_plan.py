@@ -181,14 +181,26 @@ class _DevicePlan:
         self.out_rows = torch.from_numpy(plan.out_rows.astype(np.int64)).to(device)
 
 
+_PACK_EPOCH = 0  # part of every cache stamp: invalidate_packed_weights() moves it
+
+
+def invalidate_packed_weights() -> None:
+    """Every module's cached packs become stale (library.invalidate_weight_packs: weights updated
+    by a replayed HIP graph keep their _version)."""
+    global _PACK_EPOCH
+    _PACK_EPOCH += 1
+
+
 def _packed_weights(predictor, device):
-    """Packed conv weights, cached on the module and rebuilt if any parameter changed."""
+    """Packed conv weights, cached on the module and rebuilt if any parameter changed.  While the
+    stream is capturing the cache is neither read nor written (the pack launches are recorded)."""
     import torch
     from . import _native as nat
     params = [p for blk in predictor.tcn for p in (blk.conv1.conv.weight, blk.conv2.conv.weight)]
-    stamp = tuple((p.data_ptr(), p._version) for p in params)
+    capturing = torch.cuda.is_current_stream_capturing()
+    stamp = (_PACK_EPOCH,) + tuple((p.data_ptr(), p._version) for p in params)
     cache = getattr(predictor, "_lg_tcn_packed", None)
-    if cache is not None and cache[0] == stamp:
+    if not capturing and cache is not None and cache[0] == stamp:
         return cache[1]
     lib = nat.load_library()
     n = lib.lg_tcn_packed_weight_floats(128)
@@ -199,7 +211,8 @@ def _packed_weights(predictor, device):
         out = torch.empty(n, dtype=torch.float32, device=device)
         nat.check(lib.lg_tcn_pack_weight(nat.ptr(w), nat.ptr(out), 128, nat.stream_of(w)), "lg_tcn_pack_weight")
         packed.append(out)
-    object.__setattr__(predictor, "_lg_tcn_packed", (stamp, packed))
+    if not capturing:
+        object.__setattr__(predictor, "_lg_tcn_packed", (stamp, packed))
     return packed
 
 

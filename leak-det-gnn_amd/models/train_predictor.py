@@ -10,6 +10,14 @@ DataLoader path), and checkpoints store the standardizer as plain lists of float
 load with torch.load(weights_only=True), and the reference's loaders
 (train_detector.py / event_evaluator.py: np.asarray(std_mean, dtype=np.float32) after a
 load with map_location=cuda) accept them on any device.
+
+On a ROCm GPU the step's tail is fused: the head and the loss are one op
+(loss.head_mse_loss over model.features(...), one launch each way) and clip_grad_norm_ + AdamW one
+launch (optim.ClipAdamW, whose error word is read once per epoch).  --capture on replays every
+full-size batch's step as one captured HIP graph (models/graph_step.py) and runs the tail batch
+eagerly; --capture auto (the default) captures for the archs where the captured step measured
+faster than the eager one on every round (CAPTURE_AUTO below).  --device cpu keeps
+torch's AdamW and nn.MSELoss.
 """
 from __future__ import annotations
 
@@ -28,6 +36,70 @@ from torch.utils.data import DataLoader
 from .datasets import DeviceBatchLoader, NormalPredictorDataset, ShardBatchSampler, compute_sensor_stats_from_normal
 from .predictor import NormalPredictorGRU, NormalPredictorTCN
 from .utils import now
+
+
+# --capture auto: the archs whose captured step's slowest round was below the parent step's fastest
+# (tools/kbench.py --which predictor_step)
+CAPTURE_AUTO = {"tcn": True, "gru": True}
+
+
+class PredictorFeatures(nn.Module):
+    """What graph_step.CapturedTrainStep trains: forward is the predictor's `features`, and the
+    parameters are the whole predictor's, head included (the loss function applies the head)."""
+
+    def __init__(self, predictor: nn.Module) -> None:
+        super().__init__()
+        self.predictor = predictor
+
+    def forward(self, x: torch.Tensor, x_time: torch.Tensor) -> torch.Tensor:
+        return self.predictor.features(x, x_time)
+
+
+def head_loss_fn(predictor: nn.Module):
+    """loss_fn(features, y) = head_mse_loss with `predictor.head`'s weight and bias."""
+    from .loss import head_mse_loss
+    head = predictor.head
+
+    def loss_fn(feat: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        return head_mse_loss(feat, head.weight, head.bias, y)
+    return loss_fn
+
+
+class CapturedPredictorStep:
+    """One training step of a predictor (features, head + MSE, backward, ClipAdamW with its own
+    clipping) as one replayed HIP graph: graph_step.CapturedTrainStep over PredictorFeatures,
+    built on the first batch without disturbing the parameters, the optimizer state or torch's
+    generator.  A call with (x, x_time, y) copies a batch of the same shape into the static inputs,
+    replays, and returns the (static) loss.  A replay updates the weights on the device without
+    moving their version counters, so every call ends by dropping the cached weight packs
+    (library.invalidate_weight_packs): no eager call after it reads a pack older than the weights."""
+
+    def __init__(self, predictor: nn.Module, opt, x: torch.Tensor, x_time: torch.Tensor, y: torch.Tensor,
+                 warmup: int = 2) -> None:
+        from .graph_step import CapturedTrainStep
+        self.step = CapturedTrainStep(PredictorFeatures(predictor), head_loss_fn(predictor), opt,
+                                      (x.contiguous().clone(), x_time.contiguous().clone()), y.contiguous().clone(),
+                                      clip=None, warmup=warmup, preserve_state=True)
+
+    def __call__(self, x=None, x_time=None, y=None) -> torch.Tensor:
+        from . import library
+        if x is not None:
+            self.step.inputs[0].copy_(x)
+            self.step.inputs[1].copy_(x_time)
+            self.step.label.copy_(y)
+        loss = self.step()
+        library.invalidate_weight_packs()
+        return loss
+
+
+def check_optimizer_errors(opt) -> None:
+    """Raise if a ClipAdamW launch of this optimizer set its error word (step_t[2]: a grid-barrier
+    wait timed out and that step's update is invalid)."""
+    for group in opt.param_groups:
+        st = group.get("step_t")
+        if torch.is_tensor(st) and int(st[2:3].view(torch.int32).item()) != 0:
+            raise RuntimeError("ClipAdamW reported a grid-barrier timeout (error word "
+                               f"{int(st[2:3].view(torch.int32).item())}); the parameters are invalid")
 
 
 def set_seed(seed: int) -> None:
@@ -103,6 +175,10 @@ def main(argv=None) -> None:
     ap.add_argument("--num_workers", type=int, default=0)
     ap.add_argument("--log_every", type=int, default=50)
     ap.add_argument("--loader", type=str, default="device", choices=["device", "torch"])
+    ap.add_argument("--capture", type=str, default="auto", choices=["auto", "on", "off"],
+                    help="replay each full-size training batch's step as one captured HIP graph "
+                         "(models/graph_step.py; auto = on for the GPU path where it measured faster); "
+                         "the tail batch runs eagerly")
     ap.add_argument("--profile", type=int, default=0,
                     help="torch.profiler over this many training steps (after one warm-up step): "
                          "<out_dir>/predictor_trace.json + predictor_ops.txt (models/profiling.py)")
@@ -112,6 +188,10 @@ def main(argv=None) -> None:
     out_dir.mkdir(parents=True, exist_ok=True)
     set_seed(args.seed)
     device = pick_device(args.device)
+    fused_step = device.type == "cuda"  # head + MSE as one op, clip_grad_norm_ + AdamW as one launch
+    use_graph = args.capture == "on" or (args.capture == "auto" and fused_step and CAPTURE_AUTO[args.arch])
+    if use_graph and not fused_step:
+        raise ValueError("--capture on needs the GPU path (--device cuda)")
     print(f"{now()} [predictor] device={device} seed={args.seed}")
     print(f"{now()} [predictor] loading normal data from: {args.normal_root}")
 
@@ -139,9 +219,15 @@ def main(argv=None) -> None:
     S = len(sensor_ids)
     model = (NormalPredictorTCN(num_sensors=S, time_dim=9) if args.arch == "tcn"
              else NormalPredictorGRU(num_sensors=S, time_dim=9)).to(device)
-    opt = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay,
-                            fused=(device.type == "cuda"))
-    loss_fn = nn.MSELoss()
+    clip = args.grad_clip if args.grad_clip and args.grad_clip > 0 else None
+    if fused_step:
+        from .optim import ClipAdamW
+        opt = ClipAdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_norm=clip)
+        feat_loss = head_loss_fn(model)
+    else:
+        opt = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+        loss_fn = nn.MSELoss()
+    cstep = None  # CapturedPredictorStep, built at the first full-size batch
     best_rmse = float("inf")
     best_path, last_path = out_dir / "predictor_best.ckpt", out_dir / "predictor_last.ckpt"
     meta = {"arch": args.arch, "num_sensors": S, "time_dim": 9, "l_in_steps": 36, "horizon_steps": 1,
@@ -160,12 +246,26 @@ def main(argv=None) -> None:
         for it, batch in enumerate(train_loader, start=1):
             x, x_time = batch["x"].to(device), batch["x_time"].to(device)
             y = batch["y"].to(device)[:, 0, :]
-            loss = loss_fn(model(x, x_time), y)
-            opt.zero_grad(set_to_none=True)
-            loss.backward()
-            if args.grad_clip and args.grad_clip > 0:
-                torch.nn.utils.clip_grad_norm_(model.parameters(), args.grad_clip)
-            opt.step()
+            if use_graph and x.size(0) == args.batch_size:
+                # full-size batch: the whole step (features, head + MSE, backward, clip + AdamW) as
+                # one graph replay on static inputs; the same arithmetic as the eager branch below
+                if cstep is None:
+                    cstep = CapturedPredictorStep(model, opt, x, x_time, y)
+                    loss = cstep()
+                else:
+                    loss = cstep(x, x_time, y)
+            elif fused_step:
+                loss = feat_loss(model.features(x, x_time), y)
+                opt.zero_grad(set_to_none=True)
+                loss.backward()
+                opt.step()
+            else:
+                loss = loss_fn(model(x, x_time), y)
+                opt.zero_grad(set_to_none=True)
+                loss.backward()
+                if clip is not None:
+                    torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
+                opt.step()
             running += loss.detach().double() * x.size(0)
             seen += x.size(0)
             prof.step()
@@ -173,6 +273,8 @@ def main(argv=None) -> None:
                 print(f"{now()} [predictor][epoch {epoch:02d}] step {it:05d}/{len(train_loader):05d} "
                       f"loss={running.item() / max(seen, 1):.6f}")
         train_loss = running.item() / max(seen, 1)
+        if fused_step:
+            check_optimizer_errors(opt)
         val_metrics = evaluate_predictor(model, val_loader, device, mean, std)
         print(f"{now()} [predictor][epoch {epoch:02d}] done. train_loss={train_loss:.6f} "
               f"val_mae={val_metrics['mae']:.4f} val_rmse={val_metrics['rmse']:.4f}")

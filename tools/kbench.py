@@ -1,7 +1,7 @@
 """Kernel micro-benchmark (GPU): times individual libleakgnn kernels in isolation with
 HIP events on the launch stream.  Used for tuning and under rocprofv3 --pmc.
 
-  python tools/kbench.py [--which gcn_fwd,gcn_bwd,spmm,edge_fwd,edge_bwd,gru_fwd,gru_bwd,gru_ni_fwd,gru_ni_bwd,gru_stack,gru_predictor,tcn,tcn_train] [--B 256] [--iters 50]
+  python tools/kbench.py [--which gcn_fwd,gcn_bwd,spmm,edge_fwd,edge_bwd,gru_fwd,gru_bwd,gru_ni_fwd,gru_ni_bwd,gru_stack,gru_predictor,tcn,tcn_train,predictor_step] [--B 256] [--iters 50]
 """
 import argparse
 import ctypes
@@ -926,6 +926,82 @@ def main():
         t_all, t_nodx = timeit(bwd(True), args.iters), timeit(bwd(False), args.iters)
         res["tcn_stage_bwd"] = {"us": t_all, "us_without_dx": t_nodx, "dx_us": t_all - t_nodx,
                                 "ws_MiB": ws.numel() / 2 ** 20}
+    if "predictor_step" in which:
+        # train_predictor's whole step at the CLI's shape (B, 36, 29 + 9), train mode, p = 0.1, both archs:
+        #   parent    module forward, nn.MSELoss, backward, clip_grad_norm_(1.0), torch's fused AdamW
+        #   eager     features, leakgnn::head_mse, backward, ClipAdamW(max_norm=1.0)
+        #   captured  the same step as one replayed HIP graph (train_predictor.CapturedPredictorStep)
+        # gru_stack's protocol: windows of about --window-ms, the legs alternating within a round,
+        # --rounds rounds, median with min .. max.  device_launches: the device activities (kernels,
+        # copies, fills) torch's profiler sees in one step.
+        import copy
+        from models import predictor as mpred
+        from models import train_predictor as tp
+        from models.optim import ClipAdamW
+        S, L = 29, 36
+        xb, tb, yb = torch.randn(B, L, S, device=dev), torch.randn(B, L, 9, device=dev), torch.randn(B, S, device=dev)
+
+        def window_us(fn, n):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(n):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) * 1e3 / n
+
+        def launches(fn):
+            from torch.autograd import DeviceType
+            from torch.profiler import ProfilerActivity, profile
+            try:
+                with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+                    fn()
+                    torch.cuda.synchronize()
+                return sum(1 for e in prof.events() if e.device_type == DeviceType.CUDA)
+            except Exception as e:  # noqa: BLE001  the count is a note beside the timings
+                return f"unavailable ({type(e).__name__})"
+
+        for arch in ("tcn", "gru"):
+            torch.manual_seed(0)
+            m0 = (mpred.NormalPredictorTCN(S, 9) if arch == "tcn" else mpred.NormalPredictorGRU(S, 9)).train().to(dev)
+            ma, mb, mc = m0, copy.deepcopy(m0), copy.deepcopy(m0)
+            oa = torch.optim.AdamW(ma.parameters(), lr=1e-3, weight_decay=1e-4, fused=True)
+            ob, oc = (ClipAdamW(m.parameters(), lr=1e-3, weight_decay=1e-4, max_norm=1.0) for m in (mb, mc))
+            mse, lb = torch.nn.MSELoss(), tp.head_loss_fn(mb)
+
+            def parent():
+                loss = mse(ma(xb, tb), yb)
+                oa.zero_grad(set_to_none=True)
+                loss.backward()
+                torch.nn.utils.clip_grad_norm_(ma.parameters(), 1.0)
+                oa.step()
+
+            def eager():
+                loss = lb(mb.features(xb, tb), yb)
+                ob.zero_grad(set_to_none=True)
+                loss.backward()
+                ob.step()
+            captured = tp.CapturedPredictorStep(mc, oc, xb, tb, yb)
+            fns = {"parent": parent, "eager": eager, "captured": captured}
+            iters = {}
+            for key, fn in fns.items():
+                for _ in range(3):
+                    fn()
+                torch.cuda.synchronize()
+                iters[key] = max(3, int(args.window_ms * 1e3 / window_us(fn, 3)))
+            samples = {key: [] for key in fns}
+            for _ in range(args.rounds):
+                for key, fn in fns.items():
+                    samples[key].append(window_us(fn, iters[key]))
+            leg = {"rounds": args.rounds, "window_ms": args.window_ms, "B": B}
+            for key, v in samples.items():
+                leg[key] = {"us": round(float(np.median(v)), 1), "min_max_us": [round(min(v), 1), round(max(v), 1)],
+                            "iters": iters[key], "device_launches": launches(fns[key])}
+            leg["captured_slowest_beats_parent_fastest"] = max(samples["captured"]) < min(samples["parent"])
+            leg["eager_slowest_beats_parent_fastest"] = max(samples["eager"]) < min(samples["parent"])
+            tp.check_optimizer_errors(ob)
+            tp.check_optimizer_errors(oc)
+            res[f"predictor_step_{arch}"] = leg
     for k, v in res.items():
         print(k, json.dumps({a: round(b, 2) if isinstance(b, float) else b for a, b in v.items()}))
 
