@@ -129,7 +129,12 @@ struct Nm3Lds {  // dynamic LDS layout (floats)
     // float offset of 16-byte chunk c of row r in a wave's tile
     static __device__ __forceinline__ int tix(int r, int c) { return r * NmGeo<D>::S + 4 * c; }
 };
+static_assert(Nm3Lds<64, true, 4>::BYTES <= 160 * 1024 && Nm3Lds<64, false, 4>::BYTES <= 160 * 1024 &&
+                  Nm3Lds<32, true, 4>::BYTES <= 160 * 1024 && Nm3Lds<32, false, 4>::BYTES <= 160 * 1024,
+              "LDS budget");
 
+// The two timeline instruments stay switchable: tools/kbench.py --stamps and --probe read them
+// from lab builds, and the GRU kernels' stamps share LG_NM3_STAMPS.
 #if defined(LG_NM3_STAMPS) || defined(LG_PC_PROBE)
 // kernel-lab timeline (LG_NM3_STAMPS builds only): per wave, slot 0 realtime at start, 1 clock
 // at start, 2 after the W staging barrier, 3 + 3 t .. 5 + 3 t for tile t < 6 (rows
@@ -496,6 +501,8 @@ k_gcn_fwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, c
 // protocol would end the launch with wrong results instead of a hang).
 // Transform: the 3-way bf16 split (bit-identical to k_gcn_fwd_nm3) or, F16, the 2-way fp16
 // split with power-of-two scaling (split_bf16.h; 3 MFMAs per product instead of 6).
+// The LG_PC_* numbers below select no code path; they keep their -D override so that the
+// Makefile's `lab` target (LABDEF=) can re-tune them.  R, the ring's tile slots per producer:
 #ifndef LG_PC_RING
 #define LG_PC_RING 4
 #endif
@@ -529,97 +536,37 @@ static_assert(kPcProdN <= 16 && kPcProdN * (1 + LG_PC_NC) <= 16, "ready[16]; at 
 // The node-table records of a workgroup's first kPcRecs tiles are staged in LDS with W, so a
 // producer's record is an LDS read after its tile draw instead of a scalar load from L2 (whose
 // latency sat between drawing tile t + 2 and issuing its loads, every tile); later tiles (large
-// graphs) read theirs with nm_rec.
+// graphs) read theirs with nm_rec.  Dense layers only: layer 0 on the compressed input (X0)
+// stages no records, its producers read every one with nm_rec.
 #ifndef LG_PC_RECS
 #define LG_PC_RECS 256
 #endif
 constexpr int kPcRecs = LG_PC_RECS;
-// 1: the workgroup-wide barrier at the start only covers the hand-off counters; the CONSUMER
-// waves stage W (and the bias, the max |W|) among themselves behind an LDS counter, so the
-// producers start gathering at once instead of waiting ~1.3 us for W's loads (probe, r05h/i).
-// The node-table records then come from scalar loads (nothing else to stage).  0: one barrier
-// after W and the records are staged by the whole workgroup.
-#ifndef LG_PC_WSPLIT
-#define LG_PC_WSPLIT 1
-#endif
-constexpr bool kPcWsplit = LG_PC_WSPLIT != 0;
-// lab: the split W staging on the dense layers too (LG_PC_WS_DENSE), and with it the node-table
-// records staged by the producer waves instead of read from L2 per tile (LG_PC_PREC)
-#ifndef LG_PC_WS_DENSE
-#define LG_PC_WS_DENSE 0
-#endif
-#ifndef LG_PC_PREC
-#define LG_PC_PREC 0
-#endif
-// lab: tiles dealt to a workgroup's producers statically (p, p + 4, ...) with their records
-// by scalar loads a step ahead, instead of an LDS counter and LDS-staged records
-#ifndef LG_PC_STATIC
-#define LG_PC_STATIC 0
-#endif
-// producer wave priority (s_setprio; 0: the default, equal to the consumers').  Measured (r05m,
-// isolated train mode, two rounds): 2 and 3 within the box's noise of 0 (20.5-21.3 us each)
-#ifndef LG_PC_PRIO
-#define LG_PC_PRIO 0
-#endif
-// 1: the producers' prefetch loads are issued through inline asm and waited for with explicit
+// The producers' prefetch loads are issued through inline asm and waited for with explicit
 // vmcnt counts (the other buffer's loads stay in flight).  The compiler's own wait insertion
 // lost track of the unrolled pair's two buffers (the loop it builds is irreducible) and waited
-// for every load in flight at each tile's accumulate — one tile of prefetch instead of two
-// (r05j: 10.7 us for the launch with neither loads nor consumer work, 15.1 with the loads).
+// for every load in flight at each tile's accumulate -- one tile of prefetch instead of two.
 // Its waits for loads it does see stay correct: the asm loads are older, and vmcnt counts in
-// order.  0: the builtin loads (A/B).
-#ifndef LG_PC_EARLY
-#define LG_PC_EARLY 1
-#endif
-#ifndef LG_PC_ASMLOAD
-#define LG_PC_ASMLOAD 1
-#endif
+// order.
 __device__ __forceinline__ f32x4 pc_load_b128(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff) {
-#if LG_PC_ASMLOAD
     f32x4 v;
     asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(v) : "v"(voff), "s"(rs), "s"(soff));
     return v;
-#else
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0));
-#endif
 }
 __device__ __forceinline__ uint32_t pc_load_u16(__amdgpu_buffer_rsrc_t rs, uint32_t voff) {
-#if LG_PC_ASMLOAD
     uint32_t v;
     asm volatile("buffer_load_ushort %0, %1, %2, 0 offen" : "=v"(v) : "v"(voff), "s"(rs));
     return v;
-#else
-    return __builtin_amdgcn_raw_buffer_load_b16(rs, voff, 0, 0);
-#endif
 }
 // wait until at most N of this wave's vector memory loads are in flight (asm loads only)
 template <int N>
 __device__ __forceinline__ void pc_vm_wait() {
-#if LG_PC_ASMLOAD
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N));
-#endif
 }
 template <typename T>
 __device__ __forceinline__ void pc_pin(T& v) {  // v is read only after the waits above it
-#if LG_PC_ASMLOAD
     asm volatile("" : "+v"(v));
-#else
-    (void)v;
-#endif
 }
-// lab: work moved from the consumer waves (the pipeline's bound) to the producers: the tile's
-// largest |value| for the f16 scale (LG_PC_PMAX, dense layers; word 10 of the slot metadata) and
-// the dropout row-stream seeds (LG_PC_PSEED, one per consumer lane, in LDS beside the slot);
-// LG_PC_CPRIO: consumer wave priority (s_setprio)
-#ifndef LG_PC_PMAX
-#define LG_PC_PMAX 0
-#endif
-#ifndef LG_PC_PSEED
-#define LG_PC_PSEED 0
-#endif
-#ifndef LG_PC_CPRIO
-#define LG_PC_CPRIO 0
-#endif
 // ring-slot metadata: n, b0, nb, X0's sensor entries (count, then up to kPcSens (slot, w) pairs)
 constexpr int kPcSens = 3;
 constexpr int kPcMeta = 16;
@@ -635,12 +582,13 @@ struct PcLds {  // floats
     static constexpr int FOFF = XOFF + 16;                          // ready[16], done[kPcProd * NC], fin[4], ctr
     static constexpr int MOFF = FOFF + 16 + kPcProd * NC + kPcProd + 4;  // per (producer, slot): kPcMeta words
     static constexpr int COFF = MOFF + kPcMeta * kPcProd * kPcRing;  // kPcRecs node-table records (16 words)
-    static constexpr int SOFF = COFF + 16 * kPcRecs;                  // LG_PC_PSEED: per (producer, slot) 64 row-stream seeds
-    static constexpr int ROFF = SOFF + (LG_PC_PSEED ? 64 * kPcProd * kPcRing : 0);  // the rings
+    static constexpr int ROFF = COFF + 16 * kPcRecs;                 // the rings
     static constexpr size_t BYTES = 4 * static_cast<size_t>(ROFF + kPcProd * kPcRing * TILE);
     static __device__ __forceinline__ int tix(int r, int c) { return SWZ ? r * D + 4 * (c ^ r) : r * NmGeo<D>::S + 4 * c; }
 };
 static_assert(kPcRing >= kPcNC, "a ring slot per consumer at least");
+static_assert(PcLds<64, kPcProdN, kPcNC>::BYTES <= 160 * 1024 && PcLds<32, kPcProdN, kPcNC>::BYTES <= 160 * 1024,
+              "LDS budget");
 
 __device__ __forceinline__ uint32_t pc_load_acq(const uint32_t* p) {
     return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -653,13 +601,6 @@ __device__ __forceinline__ void pc_store_rel(uint32_t* p, uint32_t v) {
 // 2: a consumer's wait for its tile), which lg_spin_errors reads back -- the launch's results
 // are then invalid.  The tests assert it stays 0 (tests/conftest.py, after every GPU module).
 __device__ uint32_t g_pc_spin_err;
-// lab (LG_PC_DYN): per-XCD tile counters (one 256-byte line each) and the producers' finish
-// counter; zero between launches (the launch's last producer resets them)
-#ifndef LG_PC_DYN
-#define LG_PC_DYN 0
-#endif
-__device__ uint32_t g_pc_dyn[8 * 64];
-__device__ uint32_t g_pc_dyn_fin;
 // wait until *p >= v (bounded: ~2^20 polls)
 __device__ __forceinline__ void pc_wait(const uint32_t* p, uint32_t v) {
     for (int it = 0; it < (1 << 20); ++it) {
@@ -772,36 +713,32 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
         nb = valid ? min(16u, B - b0) : 0u;
     };
 
-    // W (fp32, x fold) and bias to LDS by the whole workgroup (F16: and the max |W|), and the
-    // records of the workgroup's first kPcRecs tiles (every load in flight before the first store)
+    // The prologue.  The CONSUMER waves stage W (fp32, x fold), the bias and (F16) the max |W| in
+    // LDS, every load in flight before the first store; the producers start gathering meanwhile.
+    //   * kEarly, the dense layers: the producers issue their first two tiles (draws p and
+    //     kPcProd + p, the counter starting past them) before the prologue barrier, from records
+    //     read through the scalar cache, while the consumers also stage the records of the
+    //     workgroup's first kPcRecs tiles: the first gathers overlap the staging.
+    //   * kWs, layer 0 on the compressed input (X0): the barrier only covers the hand-off counters
+    //     and the consumers synchronise among themselves on an LDS counter (wrdy), so the producers
+    //     do not wait ~1.3 us for W's loads; they read every record with scalar loads.
+    // Each layer kind takes the form that measured faster for it.
+    constexpr bool kWs = X0, kEarly = !X0;
     int32_t* recs = reinterpret_cast<int32_t*>(lds + LY::COFF);
-    // the split W staging pays on layer 0 (X0: -1 us in the step) and costs the dense layers ~1 us
-    // (r05w, same box, in-graph: 22.1-22.5 against 21.0-21.1 us: their producers then read every
-    // record from L2), so only X0 takes it -- unless the producers stage the records themselves
-    // (kPrecs: after the counter barrier, synchronised among the producer waves alone)
-    constexpr bool kWs = kPcWsplit && (X0 || LG_PC_WS_DENSE);
-    constexpr bool kPrecs = kWs && LG_PC_PREC && kPcRecs > 0;
-    // LG_PC_EARLY (dense layers): the producers' first two tiles (draws p and kPcProd + p, the
-    // counter starting past them) are issued before the prologue barrier, from records read
-    // through the scalar cache, while the consumer waves alone stage W, the bias and the records:
-    // the kernel's first gathers overlap the W staging instead of following it
-    constexpr bool kEarly = LG_PC_EARLY && !kWs && !LG_PC_STATIC && !LG_PC_DYN;
-    const int nrec = ((kWs && !kPrecs) || LG_PC_STATIC || LG_PC_DYN) ? 0 : min(kPcRecs, tend > tfirst ? (tend - tfirst + tstride - 1) / tstride : 0);
+    const int nrec = X0 ? 0 : min(kPcRecs, tend > tfirst ? (tend - tfirst + tstride - 1) / tstride : 0);
     uint32_t* wrdy = ctr + 1;  // kWs: consumer waves done staging W
-    uint32_t* prdy = ctr + 2;  // kPrecs: producer waves done staging the records
     if constexpr (kWs) {
         if (threadIdx.x < 16 + kPcProd * NC) ready[threadIdx.x] = 0u;  // ready[] and done[]
         if (threadIdx.x < kPcProd) fin[threadIdx.x] = ~0u;
         if (threadIdx.x == 0) {
             *ctr = 0u;
             *wrdy = 0u;
-            *prdy = 0u;
+            ctr[2] = 0u;  // a spare counter word, cleared with its neighbours (one 12-byte LDS store)
         }
     } else {
-        // the staging threads: all of the workgroup, or (kEarly) its consumer waves
-        constexpr int SNT = kEarly ? NT - 64 * kPcProd : NT;
-        const int st = static_cast<int>(threadIdx.x) - (kEarly ? 64 * kPcProd : 0);
-        if (!kEarly || !producer) {
+        constexpr int SNT = NT - 64 * kPcProd;  // the staging threads: the consumer waves
+        const int st = static_cast<int>(threadIdx.x) - 64 * kPcProd;
+        if (!producer) {
             constexpr int W4 = D * D / 4, WPER = (W4 + SNT - 1) / SNT, RPER = kPcRecs ? (4 * kPcRecs + SNT - 1) / SNT : 1;
             f32x4 wv[WPER];
 #pragma unroll
@@ -840,29 +777,9 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
         }
         if (threadIdx.x < 16 + kPcProd * NC) ready[threadIdx.x] = 0u;  // ready[] and done[]
         if (threadIdx.x < kPcProd) fin[threadIdx.x] = ~0u;
-        if (threadIdx.x == 0) *ctr = kEarly ? 2u * kPcProd : 0u;
+        if (threadIdx.x == 0) *ctr = 2u * kPcProd;
     }
-    if (!kEarly || !producer) __syncthreads();  // kEarly: the producers arrive after their first issues
-    if (kPrecs && producer) {  // the producers' record staging (the workgroup's first nrec tiles)
-        constexpr int PT = 64 * kPcProd, RP = (4 * kPcRecs + PT - 1) / PT;
-        lg_u32x4 rv[RP];
-#pragma unroll
-        for (int u = 0; u < RP; ++u) {  // quarter (i & 3) of record i >> 2
-            const int i = u * PT + static_cast<int>(threadIdx.x);
-            if (i < 4 * nrec) {
-                uint32_t n, b0, nb;
-                tile_coords(tfirst + (i >> 2) * tstride, n, b0, nb);
-                rv[u] = reinterpret_cast<const lg_u32x4*>(tab)[4 * (static_cast<size_t>(N) + n) + (i & 3)];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < RP; ++u) {
-            const int i = u * PT + static_cast<int>(threadIdx.x);
-            if (i < 4 * nrec) reinterpret_cast<lg_u32x4*>(recs)[i] = rv[u];
-        }
-        if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(prdy, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        pc_wait(prdy, static_cast<uint32_t>(kPcProd));
-    }
+    if (kWs || !producer) __syncthreads();  // kEarly: the producers arrive after their first issues
     if (kWs && !producer) {  // the consumers' W staging (all loads in flight before the first store)
         constexpr int CT = 64 * kPcProd * NC, W4 = D * D / 4, WPER = (W4 + CT - 1) / CT;
         const int ct = static_cast<int>(threadIdx.x) - 64 * kPcProd;
@@ -905,12 +822,6 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
 
     if (producer) {
         // ---------------- producer: gather + accumulate, two tiles in flight
-        const uint32_t pkey = LG_PC_PSEED && DROP ? lg_dropout_key_dev(seed, salt) : 0u;
-#if LG_PC_PRIO
-        // the producer's instruction stream is the pipeline's critical path; its two consumers on
-        // the same SIMD have ring slack, so the producer goes first when both are ready to issue
-        __builtin_amdgcn_s_setprio(LG_PC_PRIO);
-#endif
         // X0 (layer 0 on the compressed node init): a neighbour whose record col carries
         // kLgSensorCol is a sensor row of x (= xs0 [S][B][D]) at its slot; any other
         // neighbour's block is its [x0 > 0] mask word (one uint16 per lane), x0 = bit ? v0 : 0
@@ -936,12 +847,6 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
         // X0's sensor rows are added by the consumer (ring-slot metadata), so the producer issues
         // one 2-byte load per neighbour instead of the rows.
         auto load_nb = [&](int c, bool have, uint32_t b0, const uint32_t (&lk)[G::K], f32x4 (&blk)[G::K], uint32_t& bw) {
-#ifdef LG_PC_LAB_NOLOAD  // lab: no gather loads (the neighbour blocks read as lane-dependent constants)
-            bw = lane;
-#pragma unroll
-            for (int k = 0; k < G::K; ++k) blk[k] = f32x4{1.f * k, 1.f * lane, 0.5f, 0.25f};
-            return;
-#endif
             if constexpr (X0) {
                 const bool sens = (c & kLgSensorCol) != 0;
                 bw = pc_load_u16(brs, have && !sens ? nm_mask_off(static_cast<uint32_t>(c), b0 >> 4, ngroups, lane)
@@ -987,37 +892,7 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
         };
         // the workgroup's next tile (an LDS atomic; past tend once its tiles are all dealt) and
         // its record (staged in LDS for the first kPcRecs draws)
-        uint32_t gcount = 0;  // LG_PC_STATIC: this producer's draws so far
         auto grab = [&](NmRec& r) -> int32_t {
-#if LG_PC_DYN
-            // dynamic dealing over the XCD's tile range: a global counter per XCD, one atomic per
-            // draw, requested a whole step before the tile's loads issue
-            uint32_t di = 0;
-            if (lane == 0)
-                di = __hip_atomic_fetch_add(&g_pc_dyn[64 * (blockIdx.x % 8)], 1u, __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT);
-            di = __builtin_amdgcn_readfirstlane(di);
-            const int32_t dchunk = static_cast<int32_t>((static_cast<int64_t>(ngroups) * N + 7) / 8);
-            const int32_t tile = gridDim.x >= 8 ? static_cast<int32_t>(blockIdx.x % 8) * dchunk + static_cast<int32_t>(di)
-                                                : tend;
-            {
-                uint32_t n, b0, nb;
-                tile_coords(tile, n, b0, nb);
-                r = nm_rec(tab, N + n);
-            }
-            return tile;
-#elif LG_PC_STATIC
-            // static dealing: draw i of producer p is the workgroup's tile p + 4 i; its record by
-            // scalar loads, requested a whole step before the tile's loads issue
-            const int32_t tile = tfirst + static_cast<int32_t>(gcount * kPcProd + prod) * tstride;
-            ++gcount;
-            {
-                uint32_t n, b0, nb;
-                tile_coords(tile, n, b0, nb);
-                r = nm_rec(tab, N + n);
-            }
-            return tile;
-#else
             uint32_t i = 0;
             if (lane == 0) i = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             i = __builtin_amdgcn_readfirstlane(i);
@@ -1042,7 +917,6 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
                 r = nm_rec(tab, N + n);
             }
             return tile;
-#endif
         };
         int32_t tl[2];  // the tile whose blocks are in flight in buffer b
         // r: the tile's node-table record (schedule section: slot -> record with its node id),
@@ -1150,25 +1024,11 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
             float* slot = ring + sl * LY::TILE;
 #pragma unroll
             for (int k = 0; k < G::K; ++k) st4(slot + LY::tix(G::RPI * k + rl, fg), acc[k]);
-            uint32_t pmx = 0;
-            if constexpr (LG_PC_PMAX && F16 && !X0) {  // the tile's largest |value| (the consumer's f16 scale)
-                float mf = 0.f;
-#pragma unroll
-                for (int k = 0; k < G::K; ++k)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) mf = fmaxf(mf, fabsf(acc[k][c]));
-                pmx = lg_wave_max_bits(__float_as_uint(mf));
-            }
-            if constexpr (LG_PC_PSEED && DROP) {  // the consumer lane (j, q)'s row-stream seed
-                uint32_t* sd = reinterpret_cast<uint32_t*>(lds + LY::SOFF) + 64 * (prod * R + sl);
-                sd[lane] = lg_row_stream_seed(pkey, static_cast<uint64_t>(b0 + j) * N + mn, static_cast<uint32_t>(q));
-            }
             if (lane == 0) {
                 uint32_t* m = meta + kPcMeta * (prod * R + sl);
                 m[0] = mn;
                 m[1] = b0;
                 m[2] = mnb;
-                if constexpr (LG_PC_PMAX && F16 && !X0) m[10] = pmx;
                 if constexpr (X0) {
                     m[3] = nsx;
                     m[4] = ss0;
@@ -1217,15 +1077,6 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
         // tiles are drawn in increasing order, so the first one past tend ends the producer
         pc_vm_wait<0>();  // the last (empty) prefetches
         if (lane == 0) pc_store_rel(&fin[prod], static_cast<uint32_t>(t));
-#if LG_PC_DYN
-        if (lane == 0) {  // the launch's last producer: the counters back to 0 for the next launch
-            const uint32_t f = __hip_atomic_fetch_add(&g_pc_dyn_fin, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (f + 1 == gridDim.x * kPcProd) {
-                for (int x = 0; x < 8; ++x) __hip_atomic_store(&g_pc_dyn[64 * x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&g_pc_dyn_fin, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-#endif
 #ifdef LG_NM3_STAMPS
         pc_stamp_end();
 #endif
@@ -1236,9 +1087,6 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
     }
 
     // ---------------- consumer: transform + epilogue
-#if LG_PC_CPRIO
-    __builtin_amdgcn_s_setprio(LG_PC_CPRIO);
-#endif
     const __amdgpu_buffer_rsrc_t yrs = nm_rsrc(y, bytes);
     const __amdgpu_buffer_rsrc_t srs = nm_rsrc(x, X0 ? static_cast<uint64_t>(x0.S) * B * (4u * D) : 0);  // X0: xs0
     const __amdgpu_buffer_rsrc_t mrs = nm_mask_rsrc(ymask, N, ngroups);
@@ -1248,7 +1096,7 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
     int sw = 0;  // F16: W's scale exponent
     if constexpr (F16) {
         uint32_t m = 0;
-        for (int w = (kWs || kEarly) ? kPcProd : 0; w < kPcProd * (1 + NC); ++w) m = max(m, wmx[w]);
+        for (int w = kPcProd; w < kPcProd * (1 + NC); ++w) m = max(m, wmx[w]);  // the consumer waves'
         sw = lg_f16_scale_exp(__builtin_amdgcn_readfirstlane(m));
     }
     lg_bf16x8 wf[NP][G::CH][KS];
@@ -1285,10 +1133,6 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
         const uint32_t* m = meta + kPcMeta * (prod * R + sl);
         const uint32_t n = __builtin_amdgcn_readfirstlane(m[0]), b0 = __builtin_amdgcn_readfirstlane(m[1]),
                        nb = __builtin_amdgcn_readfirstlane(m[2]);
-#ifdef LG_PC_LAB_NOCONS  // lab: consumers hand the slot straight back
-        pc_store_rel(&done[prod * NC + cons], static_cast<uint32_t>(u + 1));
-        continue;
-#endif
         f32x4 bq[KS][2];
 #pragma unroll
         for (int s2 = 0; s2 < KS; ++s2) {
@@ -1324,33 +1168,19 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
             }
         }
         uint32_t st = 0;
-        if constexpr (DROP) {
-            if constexpr (LG_PC_PSEED) st = reinterpret_cast<const uint32_t*>(lds + LY::SOFF)[64 * (prod * R + sl) + lane];
-            else st = lg_row_stream_seed(key, static_cast<uint64_t>(b0 + j) * N + n, q);
-        }
+        if constexpr (DROP) st = lg_row_stream_seed(key, static_cast<uint64_t>(b0 + j) * N + n, q);
         f32x4 o[G::CH];
-#ifdef LG_PC_LAB_NOMFMA  // lab: no transform (the tile's values stand in for the product)
-#pragma unroll
-        for (int mt = 0; mt < G::CH; ++mt) o[mt] = bq[mt % KS][mt / KS % 2];
-        if constexpr (false) {
-#else
         if constexpr (F16) {
-#endif
             // the tile's scale from its largest |value| (the B-operand values are the whole tile;
             // fmaxf on |.| source modifiers: three values an instruction)
-            int sa;
-            if constexpr (LG_PC_PMAX && !X0) {
-                sa = lg_f16_scale_exp(__builtin_amdgcn_readfirstlane(m[10]));
-            } else {
-                float mxf = 0.f;
+            float mxf = 0.f;
 #pragma unroll
-                for (int s2 = 0; s2 < KS; ++s2)
+            for (int s2 = 0; s2 < KS; ++s2)
 #pragma unroll
-                    for (int h = 0; h < 2; ++h)
+                for (int h = 0; h < 2; ++h)
 #pragma unroll
-                        for (int c = 0; c < 4; ++c) mxf = fmaxf(mxf, fabsf(bq[s2][h][c]));
-                sa = lg_f16_scale_exp(lg_wave_max_bits(__float_as_uint(mxf)));
-            }
+                    for (int c = 0; c < 4; ++c) mxf = fmaxf(mxf, fabsf(bq[s2][h][c]));
+            const int sa = lg_f16_scale_exp(lg_wave_max_bits(__float_as_uint(mxf)));
             const float sc2 = lg_pow2f(sa);
 #pragma unroll
             for (int mt = 0; mt < G::CH; ++mt) o[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1394,7 +1224,6 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
                 }
             }
         }
-#ifndef LG_PC_LAB_NOEPI  // lab: no ReLU / dropout
 #pragma unroll
         for (int mt = 0; mt < G::CH; ++mt) {
 #pragma unroll
@@ -1409,7 +1238,6 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
                 o[mt][reg] = v;
             }
         }
-#endif
         // y back through the slot (the B-operand reads above are older LDS operations of
         // this wave, so they complete first)
 #pragma unroll
@@ -1420,16 +1248,10 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
         for (int k = 0; k < G::K; ++k) {
             const uint32_t lk = (G::RPI * k + rl) < static_cast<int>(nb) ? loff[k] : kNm3RowOob;
             vk[k] = ld4(slot + LY::tix(G::RPI * k + rl, fg));
-#if !defined(LG_PC_LAB_NOSTORE) && !defined(LG_PC_LAB_NOYSTORE)  // lab: no y stores (NOSTORE: nor mask words)
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) uint32_t, vk[k]),
                                                    yrs, lk, ob, kLgActAux);
-#endif
         }
-#if defined(LG_PC_LAB_NOSTORE) || defined(LG_PC_LAB_NOMASK)
-        if (false) {
-#else
         if (ymask) {
-#endif
             uint32_t bits = 0;
 #pragma unroll
             for (int k = G::K - 1; k >= 0; --k)
@@ -1467,33 +1289,31 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
 //   dW  += t^T x     (16x16x16, K = the tile's 16 rows; t and x columns split per tile)
 // The round-1 kernel (k_gcn_bwd_nm) walked rowptr -> pair -> block as dependent round trips
 // and ran dW and dx on f32 MFMA (4096 cycles per tile against 1536 here).
-#ifndef LG_NB3_WFRAG
-#define LG_NB3_WFRAG 1  // lab: 0 = the round-5 row-major W^T planes (stride LG_NB3_SBPAD + D halves)
-#endif
-#ifndef LG_NB3_SBPAD
-#define LG_NB3_SBPAD 8
-#endif
 template <int D, bool MASK_IN>
 struct Nb3Lds {
     // W^T planes.  The dx product reads a plane as MFMA A fragments, ds_read_b128, lane (j, q)
     // at row 16 mt + j, halves 32 s2 + 8 q.  Row-major with a padded row stride, the guide's LDS
     // banking (tools/lab/lds_banks.py: lane groups {0-3, 12-15, 20-27}, ...) hits banks twice at
     // D + 8 = 72 halves on all 24 plane reads of a tile, and a conflict-free stride (80) cost
-    // VGPRs (r06f).  LG_NB3_WFRAG: the planes are stored in fragment order instead, fragment
-    // (mt, s2) a 1 KB block with lane l's 16 bytes at 16 l: every read is 64 consecutive 16-byte
-    // pieces (conflict-free), addressed by one per-lane base plus immediates, and a plane is
-    // D x D halves (no padding).  The prologue's element writes scatter (once per workgroup).
-    static constexpr int SB = LG_NB3_WFRAG ? D : (D == 64 ? D + LG_NB3_SBPAD : D + 8);
+    // VGPRs (r06f).  The planes are stored in fragment order instead, fragment (mt, s2) a 1 KB
+    // block with lane l's 16 bytes at 16 l: every read is 64 consecutive 16-byte pieces
+    // (conflict-free), addressed by one per-lane base plus immediates, and a plane is D x D
+    // halves (no padding).
+    static constexpr int SB = D;
     static constexpr int WF = (3 * D * SB) / 2;          // W^T split parts (bf16), in floats
     static constexpr int TL = 2 * NmGeo<D>::TILE;         // per wave: t tile + x tile
     static constexpr int L = D * D + 2 * D;               // slab row: dW, db, d(node bias)
     static constexpr int MX = WF + kNmBwdWaves3 * TL > L ? WF + kNmBwdWaves3 * TL : L;
     static constexpr size_t BYTES = 4 * static_cast<size_t>(MX);
 };
+static_assert(Nb3Lds<64, true>::BYTES <= 160 * 1024 && Nb3Lds<64, false>::BYTES <= 160 * 1024 &&
+                  Nb3Lds<32, true>::BYTES <= 160 * 1024 && Nb3Lds<32, false>::BYTES <= 160 * 1024,
+              "LDS budget");
 
 #ifndef LG_NB3_SPLIT
 #define LG_NB3_SPLIT 0  // lab: 1 = the tail round of k_gcn_bwd_nm3 in pieces (r06x: 50.3 vs 48.0 us, slower)
 #endif
+// a number, not a code path: the -D override is for the Makefile's `lab` target (LABDEF=)
 #ifndef LG_NB3_NPF
 #define LG_NB3_NPF 3  // neighbour blocks in flight in the backward (4: 44.6 / 40.2 against 43.2 / 38.7 us, r06zl)
 #endif
@@ -1544,23 +1364,12 @@ k_gcn_bwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, c
     const int rl = lane / G::LPR, fg = lane % G::LPR;
     float* tl = tiles + wave * LY::TL;  // t tile [row][feature], later dx
     float* xl = tl + G::TILE;           // x tile [row][feature]
-    // LDS addresses: tile row r, 16-byte chunk c4 (rows padded to G::S floats); W^T plane element
-    // (row i, column o) at wix(i, o) halves
+    // LDS addresses: tile row r, 16-byte chunk c4 (rows padded to G::S floats)
     auto tix = [&](int r, int c4) { return r * G::S + 4 * c4; };
     auto tel = [&](int r, int c) { return r * G::S + c; };
-    auto wix = [&](int i, int o) {
-        if constexpr (LG_NB3_WFRAG)  // fragment (i / 16, o / 32), lane (i % 16) + 16 ((o % 32) / 8), half o % 8
-            return (((i >> 4) * (D / 32) + (o >> 5)) * 64 + (i & 15) + 16 * ((o & 31) >> 3)) * 8 + (o & 7);
-        else
-            return i * SB + o;
-    };
-    // the A fragment (mt, s2) of lane (j, q): W^T rows 16 mt + j, columns 32 s2 + 8 q .. + 7
-    auto wrd = [&](int mt, int s2) {
-        if constexpr (LG_NB3_WFRAG)
-            return (mt * (D / 32) + s2) * 512 + 8 * lane;
-        else
-            return wix(16 * mt + j, 32 * s2 + 8 * q);
-    };
+    // the A fragment (mt, s2) of lane (j, q): W^T rows 16 mt + j, columns 32 s2 + 8 q .. + 7, in
+    // halves from the plane's start (fragment order: block (mt, s2), 8 halves per lane)
+    auto wrd = [&](int mt, int s2) { return (mt * (D / 32) + s2) * 512 + 8 * lane; };
     constexpr int WP = D * SB;  // halves per W^T plane
     const uint64_t bytes = static_cast<uint64_t>(N) * B * (4u * D);
     const __amdgpu_buffer_rsrc_t dys = nm_rsrc(dy, bytes), ms = nm_rsrc(MY ? yv : dy, bytes),
@@ -1706,11 +1515,10 @@ k_gcn_bwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, c
         }
         sW = lg_f16_scale_exp_c(lg_wave_max_bits(m));
     }
-    if constexpr (LG_NB3_WFRAG) {
+    {
         // fragment (mt, s2), lane l: W^T rows 16 mt + (l & 15), columns 32 s2 + 8 (l >> 4) .. + 7,
         // i.e. W[o][i] for 8 consecutive o: column reads of W (16 lanes = 64 contiguous bytes) and
-        // one 16-byte LDS store per plane (64 consecutive pieces).  The per-element form (4 float4
-        // reads, 48 2-byte LDS stores a thread) left the waves 9.3 us from start to this barrier (r06y).
+        // one 16-byte LDS store per plane (64 consecutive pieces).
         constexpr int CH = D / 16, KS = D / 32, NF = CH * KS * 64, NT3 = 64 * kNmBwdWaves3;
         constexpr int IT = (NF + NT3 - 1) / NT3;
         f32x4 wu[IT], wv[IT];
@@ -1747,48 +1555,6 @@ k_gcn_bwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, c
                 if constexpr (!BF) {
                     *reinterpret_cast<lg_bf16x8*>(dst + WP) = h1;
                     *reinterpret_cast<lg_bf16x8*>(dst + 2 * WP) = h2;
-                }
-            }
-        }
-    } else {
-    {
-            constexpr int W4 = D * D / 4, WPER = (W4 + 64 * kNmBwdWaves3 - 1) / (64 * kNmBwdWaves3);
-            f32x4 wv[WPER];
-    #pragma unroll
-            for (int u = 0; u < WPER; ++u) wv[u] = ld4(W + 4 * min<int>(u * 64 * kNmBwdWaves3 + threadIdx.x, W4 - 1));
-            // the first tile's loads AFTER W's: vmcnt counts in order, so the staging below waits for
-            // W alone (issued first, the staging waited for the tile's 20 gathered blocks as well:
-            // 9.3 us from start to the barrier, r06y)
-            {
-                uint32_t n0, b00, nb00, rl00;
-                tile_coords(tfirst, n0, b00, nb00, rl00);
-                issue(nm_rec(tab, N + n0), n0, b00, nb00, rl00, pslot_of(n0));  // schedule section
-            }
-            const float wsc = lg_pow2f(sW);
-    #pragma unroll
-            for (int u = 0; u < WPER; ++u) {
-                const int i4 = u * 64 * kNmBwdWaves3 + threadIdx.x;
-                if (i4 >= W4) continue;
-                const int o = i4 / (D / 4), c4 = 4 * (i4 % (D / 4));
-    #pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int e = wix(c4 + c, o);
-                    const float w = wv[u][c];
-                    if constexpr (F16) {
-                        const _Float16 h0 = static_cast<_Float16>(w * wsc);
-                        const _Float16 h1 = static_cast<_Float16>(w * wsc - static_cast<float>(h0));
-                        wsl[e] = __builtin_bit_cast(uint16_t, h0);
-                        wsl[WP + e] = __builtin_bit_cast(uint16_t, h1);
-                        continue;
-                    }
-                    const uint16_t h0 = __builtin_bit_cast(uint16_t, static_cast<__bf16>(w));
-                    const float r1 = w - __uint_as_float(static_cast<uint32_t>(h0) << 16);
-                    const uint16_t h1 = __builtin_bit_cast(uint16_t, static_cast<__bf16>(r1));
-                    const float r2 = r1 - __uint_as_float(static_cast<uint32_t>(h1) << 16);
-                    const uint16_t h2 = __builtin_bit_cast(uint16_t, static_cast<__bf16>(r2));
-                    wsl[e] = h0;
-                    wsl[WP + e] = h1;
-                    wsl[2 * WP + e] = h2;
                 }
             }
         }
@@ -2147,7 +1913,7 @@ constexpr int kRowWaves = 4;
 #define LG_ROWS_FWD_NB 4  // inline neighbours per gather batch (x 4 rows per lane; 2 / 3 / 4 / 6 measured, profiles/r03/r03ad)
 #endif
 #ifndef LG_ROWS_BWD_NB
-#define LG_ROWS_BWD_NB 4
+#define LG_ROWS_BWD_NB 4  // the same for the backward; both are numbers a lab build re-tunes (-D), not code paths
 #endif
 
 template <int n>

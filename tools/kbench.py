@@ -294,12 +294,15 @@ def main():
                                                    "4 nosplit; LEAKGNN_LIB=lib/lab build only)")
     ap.add_argument("--edgebwdlab", default="", help="comma list of streamed EdgeHead backward lab bits (1 no dW1 "
                                                       "MFMA, 2 no dfeat MFMA, 4 no scatter; LEAKGNN_LIB=lib/lab only)")
-    ap.add_argument("--nmlab", default="", help="comma list of lg_gcn_fwd_nm schedules: v1 or bpc<n> (train mode)")
+    ap.add_argument("--nmlab", default="", help="comma list of lg_gcn_fwd_nm_bits forms, each of dflt|x3|nm3|f32|bf16|pc|mask "
+                                                 "joined with + (eval and train mode)")
     ap.add_argument("--eager", action="store_true", help="time eager launches instead of a replayed HIP graph")
     ap.add_argument("--stamps", action="store_true", help="per-wave timeline of each --nmlab train launch "
-                                                           "(LEAKGNN_LIB=lib/lab_stamps build only)")
+                                                           "(LEAKGNN_LIB=lib/lab_stamps/libleakgnn.so, built by `make "
+                                                           "lab LABNAME=lab_stamps LABDEF=-DLG_NM3_STAMPS`)")
     ap.add_argument("--probe", action="store_true", help="product-speed start/end timeline of each --nmlab train "
-                                                          "launch of k_gcn_fwd_pc (LEAKGNN_LIB=lib/probe build only)")
+                                                          "launch of k_gcn_fwd_pc (LEAKGNN_LIB=lib/probe/libleakgnn.so, "
+                                                          "built by `make lab LABNAME=probe LABDEF=-DLG_PC_PROBE`)")
     ap.add_argument("--rounds", type=int, default=7, help="gru_stack leg: rounds of alternating windows")
     ap.add_argument("--window-ms", type=float, default=250.0, help="gru_stack leg: device time per timed window")
     args = ap.parse_args()
