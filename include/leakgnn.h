@@ -299,6 +299,27 @@ int lg_gcn_norm_bwd(const float* G, const int32_t* rowptr, const int32_t* col, c
 int lg_sddmm_cols(const int32_t* rowptr, const int32_t* col, const float* a, int64_t lda,
                   const float* b, int64_t ldb, float* out, int64_t N, int64_t C, lg_stream_t stream);
 
+/* dL/dw of one node-major GCN layer y = dropout(relu(Ahat x W^T + b)) with respect to the
+ * coefficients w[k] of Ahat (learned edge weights on the trunk; x, y, dy : fp32 [N][B][D]):
+ *   dz   = LG_F_MASK_IN ? dy * scale * [y > 0] : dy        (lg_gcn_bwd_nm's dz, same flag)
+ *   da   = dz W                                             (W : fp32 [D][D], nn.Linear layout)
+ *   G[k] = sum_b sum_d da[n][b][d] * x[col[k]][b][d]        for every slot k of row n
+ * over the FORWARD CSR rowptr / col of lg_graph_build[_w]; G : fp32 [nnz_cap], slots past
+ * rowptr[N] written as 0.  Under LG_F_MASK_IN the mask comes from ymask when non-NULL (the
+ * words of lg_gcn_fwd_nm_bits; y may then be NULL), else from y.  One wave per tile (one node
+ * x 16 windows x D), the tiles spread over (node, window tile): dz through LDS, da in exact
+ * fp32 with W staged once per workgroup, each neighbour block one contiguous 16 x D load, one
+ * partial per (tile, slot) from a fixed-shape wave reduction; a second launch adds a slot's
+ * partials in ascending tile order in fp64.  No atomics: two runs give the same bits.  Any
+ * B >= 1 (rows of a ragged last tile are never read), D in {32, 64}, N*B*D*4 <= 0x7FFFF000
+ * (LG_EUNSUPPORTED otherwise).  workspace: lg_sddmm_nm_workspace_bytes(B, nnz_cap) bytes,
+ * 16-byte aligned; fewer is LG_EINVAL.  (Added to ABI 26 without a bump.) */
+int64_t lg_sddmm_nm_workspace_bytes(int64_t B, int64_t nnz_cap);
+int lg_sddmm_nm(const int32_t* rowptr, const int32_t* col, const float* dy, const float* y,
+                const uint16_t* ymask, const float* W, const float* x, float* G, int64_t B, int64_t N,
+                int64_t D, int64_t nnz_cap, int flags, float scale, void* workspace, int64_t ws_bytes,
+                lg_stream_t stream);
+
 /* Node table of the node-major kernels, once per graph (and once for the transposed CSR):
  * one 64-byte record per node = {e0, e1, (col, float_as_int(w)) x 6, self, node} so a tile
  * reads its CSR row with ONE scalar load.  self = position (< 6) of the row's entry whose

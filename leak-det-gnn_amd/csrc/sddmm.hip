@@ -122,6 +122,149 @@ void dispatch_sddmm(int64_t units, bool i32, unsigned grid, hipStream_t s, const
     else launch_sddmm<V, 64, 4>(i32, grid, s, rowptr, col, a, lda, b, ldb, out, N, C);
 }
 
+// ---------------------------------------------------------------------------- lg_sddmm_nm
+// dL/dw of one node-major GCN layer (include/leakgnn.h): G[k] = sum_b da[n][b] . x[col k][b] with
+// da = dz W formed on chip.  A tile is one node x 16 windows x D, one wave per tile, the waves
+// spread over (node, window tile) so that 661 nodes still fill the machine.  Every global
+// access of a tile is the trunk kernels' flat block: lane l, unit j holds the four floats at
+// (j * 64 + l) * 4 of the contiguous 16 x D block, i.e. row j * RPP + l / LPR, channels
+// 4 (l % LPR) .. + 3 — also the layout of the mask words (bit 4 j + i of lane l).
+//   1. dz = dy (* scale * [y > 0] or the mask bit under LG_F_MASK_IN) goes to the wave's LDS tile
+//      (rows padded by 4 floats: the four rows a pass reads sit in different banks);
+//   2. da = dz W in exact fp32 FMA with W staged once per workgroup: lane (l, j) needs row
+//      j * RPP + l / LPR of dz against columns 4 (l % LPR) .. + 3 of W, so da comes out in the
+//      flat layout and needs no second trip through LDS.  (16 x D x D flops per tile against
+//      (2 + deg) x 16 x D x 4 bytes of loads: the transform is not what the kernel waits for,
+//      and fp32 FMA keeps da exact where a split-bf16 MFMA would add its 1e-7.)
+//   3. per CSR slot of the node, two at a time: the neighbour's 16 x D block in the same flat
+//      layout (one coalesced 16-byte load per lane and unit; rows past B are not read), a dot
+//      product per lane, a fixed-shape xor butterfly over the wave, one partial per (tile, slot).
+// k_sddmm_nm_reduce then adds a slot's partials in ascending tile order in fp64 and writes 0
+// to the slots past rowptr[N].  No atomics; 32-bit element offsets (N * B * D * 4 < 2^31).
+constexpr int kSddmmNmWaves = 4;
+
+__device__ __forceinline__ void wave_sync_sd() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ float dot4(f32x4 a, f32x4 b, float s) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s = fmaf(a[i], b[i], s);
+    return s;
+}
+
+template <int D>
+__global__ void __launch_bounds__(64 * kSddmmNmWaves)
+    k_sddmm_nm(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ dy,
+               const float* __restrict__ y, const uint16_t* __restrict__ ymask, const float* __restrict__ W,
+               const float* __restrict__ x, float* __restrict__ part, int B, int N, int T, int cap, int mask_in,
+               float scale) {
+    constexpr int NJ = D / 16;    // 16-byte units per lane and tile
+    constexpr int LPR = D / 4;    // lanes per row
+    constexpr int RPP = 64 / LPR; // rows per unit
+    constexpr int LD = D + 4;     // padded row of the dz tile
+    __shared__ __attribute__((aligned(16))) float sW[D * D];
+    __shared__ __attribute__((aligned(16))) float sZ[kSddmmNmWaves][16 * LD];
+    for (int i = threadIdx.x; i < D * D / 4; i += 64 * kSddmmNmWaves) st4(sW + 4 * i, ld4(W + 4 * i));
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+    const int r0 = lane / LPR, c0 = (lane % LPR) * 4;
+    float* z = sZ[wv];
+    const int ntiles = N * T;  // < 2^27: N * B * D * 4 < 2^31 and T <= (B + 15) / 16
+    for (int tile = blockIdx.x * kSddmmNmWaves + wv; tile < ntiles; tile += gridDim.x * kSddmmNmWaves) {
+        const int n = tile / T, t = tile - n * T;
+        const uint32_t own = (static_cast<uint32_t>(n) * B + t * 16) * D;  // the tile's own block of dy / y
+        const uint32_t word = mask_in && ymask ? ymask[(static_cast<uint32_t>(n) * T + t) * 64 + lane] : 0u;
+        bool live[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            live[j] = t * 16 + j * RPP + r0 < B;  // a ragged last tile: rows past B are never read
+            f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (live[j]) {
+                const uint32_t e = own + (j * 64 + lane) * 4;
+                v = ld4(dy + e);
+                if (mask_in) {
+                    if (ymask) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) v[i] = (word >> (4 * j + i)) & 1u ? v[i] * scale : 0.f;
+                    } else {
+                        const f32x4 yv = ld4(y + e);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) v[i] = yv[i] > 0.f ? v[i] * scale : 0.f;
+                    }
+                }
+            }
+            st4(z + (j * RPP + r0) * LD + c0, v);
+        }
+        wave_sync_sd();
+        f32x4 da[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) da[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+        for (int o = 0; o < D; o += 4) {
+            f32x4 wr[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) wr[i] = ld4(sW + (o + i) * D + c0);
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const f32x4 zv = ld4(z + (j * RPP + r0) * LD + o);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) da[j] += zv[i] * wr[i];
+            }
+        }
+        wave_sync_sd();  // the next tile's stores wait for these reads
+        int e0 = rowptr[n], e1 = rowptr[n + 1];
+        if (e0 < 0 || e1 > cap || e0 > e1) e0 = e1 = 0;  // a malformed CSR never writes out of range
+        float* prow = part + static_cast<size_t>(t) * cap;
+#pragma unroll 1
+        for (int k = e0; k < e1; k += 2) {
+            const bool two = k + 1 < e1;
+            int ca = col[k], cb = two ? col[k + 1] : 0;
+            if (ca < 0 || ca >= N) ca = 0;  // nor reads out of range
+            if (cb < 0 || cb >= N) cb = 0;
+            const float* xa = x + (static_cast<uint32_t>(ca) * B + t * 16) * D + lane * 4;
+            const float* xb = x + (static_cast<uint32_t>(cb) * B + t * 16) * D + lane * 4;
+            f32x4 va[NJ], vb[NJ];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {  // both blocks in flight before the first use
+                va[j] = live[j] ? ld4(xa + j * 256) : f32x4{0.f, 0.f, 0.f, 0.f};
+                vb[j] = (live[j] && two) ? ld4(xb + j * 256) : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            float sa = 0.f, sb = 0.f;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                sa = dot4(da[j], va[j], sa);
+                sb = dot4(da[j], vb[j], sb);
+            }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                sa += __shfl_xor(sa, off, 64);
+                sb += __shfl_xor(sb, off, 64);
+            }
+            if (lane == 0) {
+                prow[k] = sa;
+                if (two) prow[k + 1] = sb;
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_sddmm_nm_reduce(const float* __restrict__ part,
+                                                         const int32_t* __restrict__ rowptr, float* __restrict__ G,
+                                                         int T, int cap, int N) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= cap) return;
+    int nnz = rowptr[N];
+    nnz = nnz < 0 ? 0 : (nnz > cap ? cap : nnz);
+    double acc = 0.0;
+    if (k < nnz)
+        for (int t = 0; t < T; ++t) acc += static_cast<double>(part[static_cast<size_t>(t) * cap + k]);
+    G[k] = static_cast<float>(acc);
+}
+
 }  // namespace
 
 extern "C" int lg_sddmm_cols(const int32_t* rowptr, const int32_t* col, const float* a, int64_t lda, const float* b,
@@ -138,6 +281,51 @@ extern "C" int lg_sddmm_cols(const int32_t* rowptr, const int32_t* col, const fl
     const unsigned grid = static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>((N + 3) / 4, 8LL * lg_num_cus())));
     if (vec) dispatch_sddmm<4>(C / 4, i32, grid, s, rowptr, col, a, lda, b, ldb, out, N, C);
     else dispatch_sddmm<1>(C, i32, grid, s, rowptr, col, a, lda, b, ldb, out, N, C);
+    LG_RET_IF_LAUNCH_FAILED();
+    return LG_OK;
+}
+
+extern "C" int64_t lg_sddmm_nm_workspace_bytes(int64_t B, int64_t nnz_cap) {
+    if (B < 1 || nnz_cap < 0) return 0;
+    return ((B + 15) / 16) * nnz_cap * static_cast<int64_t>(sizeof(float));
+}
+
+extern "C" int lg_sddmm_nm(const int32_t* rowptr, const int32_t* col, const float* dy, const float* y,
+                           const uint16_t* ymask, const float* W, const float* x, float* G, int64_t B, int64_t N,
+                           int64_t D, int64_t nnz_cap, int flags, float scale, void* workspace, int64_t ws_bytes,
+                           lg_stream_t stream) {
+    if (B < 1 || N < 0 || nnz_cap < 0) return LG_EINVAL;
+    if (D != 32 && D != 64) return LG_EUNSUPPORTED;
+    if (flags & ~LG_F_MASK_IN) return LG_EUNSUPPORTED;
+    if (N * B * D * 4 > 0x7FFFF000LL) return LG_EUNSUPPORTED;  // 32-bit element offsets, as the trunk kernels
+    const int64_t T = (B + 15) / 16;
+    if (T * nnz_cap > INT32_MAX) return LG_EUNSUPPORTED;
+    if (nnz_cap == 0) return LG_OK;
+    if (!rowptr || !G) return LG_EINVAL;
+    if (ws_bytes < lg_sddmm_nm_workspace_bytes(B, nnz_cap) || !workspace) return LG_EINVAL;
+    const bool mask_in = (flags & LG_F_MASK_IN) != 0;
+    hipStream_t s = lg_stream(stream);
+    float* part = static_cast<float*>(workspace);
+    if (N > 0) {
+        if (!col || !dy || !W || !x || (mask_in && !y && !ymask)) return LG_EINVAL;
+        for (const void* p : {static_cast<const void*>(dy), static_cast<const void*>(y), static_cast<const void*>(W),
+                              static_cast<const void*>(x), static_cast<const void*>(part)})
+            if (reinterpret_cast<uintptr_t>(p) % 16 != 0) return LG_EINVAL;
+        const int64_t ntiles = N * T;
+        const unsigned grid = static_cast<unsigned>(
+            std::max<int64_t>(1, std::min<int64_t>((ntiles + kSddmmNmWaves - 1) / kSddmmNmWaves, 4LL * lg_num_cus())));
+        const int Bi = static_cast<int>(B), Ni = static_cast<int>(N), Ti = static_cast<int>(T);
+        const int capi = static_cast<int>(nnz_cap);
+        if (D == 64)
+            lg_launch(k_sddmm_nm<64>, grid, 64 * kSddmmNmWaves, 0, s, rowptr, col, dy, y, ymask, W, x, part, Bi, Ni, Ti,
+                      capi, static_cast<int>(mask_in), scale);
+        else
+            lg_launch(k_sddmm_nm<32>, grid, 64 * kSddmmNmWaves, 0, s, rowptr, col, dy, y, ymask, W, x, part, Bi, Ni, Ti,
+                      capi, static_cast<int>(mask_in), scale);
+        LG_RET_IF_LAUNCH_FAILED();
+    }
+    lg_launch(k_sddmm_nm_reduce, static_cast<unsigned>((nnz_cap + 255) / 256), 256, 0, s, part, rowptr, G,
+              static_cast<int>(T), static_cast<int>(nnz_cap), static_cast<int>(N));
     LG_RET_IF_LAUNCH_FAILED();
     return LG_OK;
 }

@@ -62,6 +62,9 @@ SIGNATURES = {
     "lg_gcn_norm_bwd_workspace_bytes": (_i64, [_i64, _i64]),
     "lg_gcn_norm_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _f32, _p, _p, _i64, _p]),
     "lg_sddmm_cols": (_i32, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _i64, _p]),
+    # dL/dw of a node-major trunk layer (added to ABI 26 without a bump: additions only)
+    "lg_sddmm_nm_workspace_bytes": (_i64, [_i64, _i64]),
+    "lg_sddmm_nm": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _f32, _p, _i64, _p]),
     "lg_nm_table_build": (_i32, [_p, _p, _i64, _p, _p, _p]),
     "lg_rcm_order": (_i32, [_p, _i64, _i64, _p]),
     "lg_incidence_workspace_bytes": (_i64, [_i64, _i64]),

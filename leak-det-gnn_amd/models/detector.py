@@ -28,6 +28,13 @@ gnn_trunk / detector_heads) and models/loss.py (leakgnn::cross_entropy):
   * the loss (CrossEntropyLoss) and, in the training scripts, clip_grad_norm_ + AdamW
     (models/optim.py).
 There is no CPU path: forward raises on CPU tensors.
+
+Edge weights (LeakDetector(..., edge_weight=, learn_edge_weight=); not in the reference, whose
+GCNConv calls pass none): one positive weight per link of the .inp link table, shared by the
+link's two directed edges, through PyG's weighted gcn_norm (lg_graph_build_w).  Fixed weights
+are a buffer (`edge_weight`); learned ones a parameter `edge_log_weight` = log of the link
+weight, whose gradient comes through the trunk ops' edge_w input (library._layer_dw,
+lg_sddmm_nm).  With neither, nothing differs from the unweighted detector.
 """
 from __future__ import annotations
 
@@ -40,7 +47,7 @@ import torch.nn.functional as F
 
 from . import library, ops
 from .gcn import GCNConv, global_mean_pool  # noqa: F401  (re-exported PyG-compatible API)
-from .utils import WDNGraph, build_wdn_graph_from_inp
+from .utils import WDNGraph, build_wdn_graph_from_inp, link_edge_weights
 
 
 class SharedSensorGRUEncoder(nn.Module):
@@ -116,16 +123,60 @@ def _batchify_edge_index(edge_index_single: torch.Tensor, num_nodes: int, batch_
     return ops.batchify_edge_index(edge_index_single, num_nodes, batch_size)
 
 
+class _EdgeWeightAnchor(torch.autograd.Function):
+    """The graph's normalised coefficients w as a function of the learned link log-weights,
+    WITHOUT device work in the forward: the values were computed when the graph was last
+    reweighted (GCNGraph.reweight, under no_grad), and every forward that wants the gradient
+    hangs a fresh autograd edge on them, so two backward passes between two optimizer steps
+    need no second reweight.  backward: dL/dw -> per directed edge (leakgnn::gcn_edge_norm_backward,
+    lg_gcn_norm_bwd) -> per link (the sum of a link's two edges: repeat_interleave(2)'s
+    backward) -> times the link weight (exp's backward)."""
+
+    @staticmethod
+    def forward(ctx, log_w: torch.Tensor, g) -> torch.Tensor:
+        ctx.norm = (g.normalize, g.fill)
+        # the tensors of THIS reweight: a later one replaces g's attributes, not these
+        ctx.save_for_backward(g.edge_weight, g.dis, g.rowptr, g.col, g.eid, g.rowptr_t, g.col_t, g.eid_t)
+        return g.w.detach()
+
+    @staticmethod
+    def backward(ctx, dw: torch.Tensor):
+        per_edge = ctx.saved_tensors[0]
+        dv = torch.ops.leakgnn.gcn_edge_norm_backward(dw.contiguous(), *ctx.saved_tensors, *ctx.norm)
+        return dv.view(-1, 2).sum(dim=1) * per_edge.view(-1, 2)[:, 0], None
+
+
+def check_link_weight(edge_weight: torch.Tensor, n_links: int) -> torch.Tensor:
+    """A positive floating tensor of shape (n_links,), checked on the host (ops.check_edge_weight's
+    rules, plus positivity: a link weight is a length or a conductance, and its log is learned)."""
+    try:
+        ops.check_edge_weight(edge_weight, n_links)
+    except ValueError as e:
+        raise ValueError(str(e) + " (one weight per link of the .inp link table)") from None
+    if n_links and not bool((edge_weight.detach() > 0).all()):
+        raise ValueError(f"edge_weight must be positive (shape ({n_links},), one weight per link)")
+    return edge_weight
+
+
 class LeakDetector(nn.Module):
     """residual (B, L_det, S), tfeat (B, L_det, 9) -> logits (B, num_pipes + 1); class P = no leak."""
 
     def __init__(self, inp_path: str | Path, sensor_node_ids: Sequence[str], pipe_ids_in_order: Sequence[str],
                  sensor_hidden: int = 64, node_hidden: int = 64, gnn_layers: int = 2, dropout: float = 0.1,
                  use_time: bool = True, include_links: Sequence[str] = ("PIPES", "PUMPS", "VALVES"),
-                 mlp_dtype: str = "fp32", sensor_layers: int = 1, sensor_dropout: float = 0.0) -> None:
+                 mlp_dtype: str = "fp32", sensor_layers: int = 1, sensor_dropout: float = 0.0,
+                 edge_weight: Optional[torch.Tensor] = None, learn_edge_weight: bool = False) -> None:
+        """edge_weight: None, or a positive floating (n_links,) tensor, one weight per link in the
+        order of the link table build_wdn_graph_from_inp walks (utils.link_edge_weights builds one
+        from the .inp file); link j is the directed edges 2j and 2j + 1 of edge_index_single.
+        learn_edge_weight: the link weights are learned, exp(edge_log_weight), starting from
+        edge_weight (or 1)."""
         super().__init__()
         if mlp_dtype not in ("fp32", "bf16"):
             raise ValueError(f"mlp_dtype must be 'fp32' or 'bf16', got {mlp_dtype!r}")
+        if learn_edge_weight and mlp_dtype == "bf16":
+            raise NotImplementedError("learn_edge_weight=True needs mlp_dtype='fp32': the gradient of the edge "
+                                      "weights through the trunk (lg_sddmm_nm) exists on the fp32 tier only")
         # "bf16": BASELINE configs[2]'s tier — the GCN transforms and the EdgeHead MLP as one
         # bf16 MFMA product with fp32 accumulate (LG_F_BF16); activations stay fp32.  Not an
         # fp32-parity mode (2e-2 relative on logits, SURVEY §7).  Not a state-dict entry.
@@ -174,6 +225,23 @@ class LeakDetector(nn.Module):
         self.fuse_encoder = True
         self.boundary: Optional[torch.Tensor] = None
         self._batched_edges: Dict[tuple, torch.Tensor] = {}  # (B, device) -> (2, B*E): the general path's edge_index
+        # edge weights: a buffer `edge_weight` (fixed) or a parameter `edge_log_weight` (learned),
+        # both (n_links,); neither: the unweighted graph, no state-dict entry
+        self.learn_edge_weight = bool(learn_edge_weight)
+        n_links = self.edge_index_single.size(1) // 2
+        assert 2 * n_links == self.edge_index_single.size(1), "make_undirected=True gives two directed edges per link"
+        if edge_weight is not None:
+            edge_weight = check_link_weight(edge_weight, n_links).detach().to(torch.float32)
+        if self.learn_edge_weight:
+            self.edge_log_weight = nn.Parameter(edge_weight.log() if edge_weight is not None else torch.zeros(n_links))
+        elif edge_weight is not None:
+            self.register_buffer("edge_weight", edge_weight.clone(), persistent=True)
+        self.weighted = self.learn_edge_weight or edge_weight is not None
+        # device -> (tensor, _version) of the weights the device graph was last built from; None
+        # after a reweight recorded into a HIP graph (its replays move the weights, not _version)
+        self._ew_stamp: Dict[torch.device, Optional[tuple]] = {}
+        self._reweights = 0  # GCNGraph.reweight calls so far (tests: an unchanged version launches none)
+        self._batched_weights: Dict[tuple, tuple] = {}  # (B, device) -> (stamp, (B*E,)): the general path's fixed weights
 
     def overlap_split(self):
         """Parameters whose gradients are final once the backward reaches `boundary` (the
@@ -185,7 +253,11 @@ class LeakDetector(nn.Module):
         st = self._dev_state.get(device)
         if st is None:
             N = len(self.node_names)
-            graph = ops.GCNGraph.build(self.edge_index_single, N, device, add_self_loops=True, normalize=True)
+            src = self._link_weight_source()
+            graph = ops.GCNGraph.build(self.edge_index_single, N, device, add_self_loops=True, normalize=True,
+                                       edge_weight=self._per_edge_weights(device) if self.weighted else None)
+            if self.weighted:
+                self._ew_stamp[device] = (src, src._version)
             inc = ops.Incidence.build(self.pipe_ends, N, device, schedule=self.incidence_schedule)
             slot = torch.full((N,), -1, dtype=torch.int32)
             for s, n in enumerate(self.sensor_node_idx.tolist()):
@@ -197,6 +269,46 @@ class LeakDetector(nn.Module):
                   None if bool(live.all()) else live.to(device), nonsensor.to(device))
             self._dev_state[device] = st
         return st
+
+    def _link_weight_source(self) -> Optional[torch.Tensor]:
+        """The state-dict tensor the link weights come from (None: unweighted)."""
+        if self.learn_edge_weight:
+            return self.edge_log_weight
+        return self.edge_weight if self.weighted else None
+
+    def _per_edge_weights(self, device: torch.device) -> torch.Tensor:
+        """(E,) weights of edge_index_single's directed edges: link j's weight at 2j and 2j + 1.
+        Carries the autograd edge to edge_log_weight when the weights learn (the general path)."""
+        src = self._link_weight_source()
+        w = src.exp() if self.learn_edge_weight else src
+        return w.to(device=device, dtype=torch.float32).repeat_interleave(2)
+
+    def _sync_edge_weights(self, graph, device: torch.device) -> None:
+        """Bring the device graph up to the current link weights: when the source tensor's
+        _version has moved since the graph was last built from it (an optimizer step, a
+        load_state_dict), GCNGraph.reweight (device work only) and the sensor-marked tables
+        refreshed in place.  An unchanged version does nothing, so an eval loop never reweights.
+        While a HIP graph is being captured the launches of LEARNED weights are always recorded (every replay then
+        reweights from the weights it finds) and the stamp is dropped, as a replayed optimizer
+        step moves no _version: the next eager forward reweights again."""
+        src = self._link_weight_source()
+        # (fixed weights are a buffer no captured step writes: they follow the stamp alone)
+        capturing = self.learn_edge_weight and torch.cuda.is_current_stream_capturing()
+        stamp = self._ew_stamp.get(device)
+        if not capturing and stamp is not None and stamp[0] is src and stamp[1] == src._version:
+            return
+        with torch.no_grad():
+            graph.reweight(self._per_edge_weights(device))
+        self._reweights += 1
+        if graph.x0marks is not None:
+            graph.x0marks.refresh(graph)
+        self._ew_stamp[device] = None if capturing else (src, src._version)
+
+    def invalidate_edge_weights(self) -> None:
+        """Forget which weights the device graphs were built from: the next forward reweights.
+        For whoever changes the weights without moving their _version, i.e. replays a HIP graph
+        that holds an optimizer step (the training CLI, after each replay).  No device work."""
+        self._ew_stamp.clear()
 
     def _x0marks(self, graph, slot: torch.Tensor):
         """The compressed layer-0 input's sensor-marked node tables (lg_nm_table_sensor_mark),
@@ -252,8 +364,18 @@ class LeakDetector(nn.Module):
         if ei is None:
             ei = _batchify_edge_index(self.edge_index_single.to(dev), N, B)
             self._batched_edges[(B, dev)] = ei
+        ew = None
+        if self.learn_edge_weight:
+            ew = self._per_edge_weights(dev).repeat(B)  # column b*E + e is edge e; autograd to edge_log_weight
+        elif self.weighted:
+            src = self.edge_weight
+            hit = self._batched_weights.get((B, dev))
+            if hit is None or hit[0] != (src.data_ptr(), src._version):
+                hit = ((src.data_ptr(), src._version), self._per_edge_weights(dev).repeat(B))
+                self._batched_weights[(B, dev)] = hit
+            ew = hit[1]
         for conv in self.convs:
-            x = F.dropout(F.relu(conv(x, ei)), p, self.training)
+            x = F.dropout(F.relu(conv(x, ei) if ew is None else conv(x, ei, ew)), p, self.training)
         h_nodes = x.view(B, N, -1)
         ends = inc.ends.long()
         pipe_logits = self.edge_head(h_nodes[:, ends[:, 0]], h_nodes[:, ends[:, 1]])     # (B, P)
@@ -275,6 +397,11 @@ class LeakDetector(nn.Module):
         g = graph
         bf16 = self.mlp_dtype == "bf16"
         enc = self.sensor_encoder
+        edge_w = None
+        if self.weighted:
+            self._sync_edge_weights(g, residual.device)
+            if self.learn_edge_weight and torch.is_grad_enabled() and self.edge_log_weight.requires_grad:
+                edge_w = _EdgeWeightAnchor.apply(self.edge_log_weight, g)
         if enc.use_time and tfeat is None:
             raise ValueError("tfeat required when use_time=True")
         if self._fused_encoder(residual, tfeat, B, N, D, nm):
@@ -282,12 +409,13 @@ class LeakDetector(nn.Module):
             mk = self._x0marks(g, slot)
             gw = [f(t) for t in (enc.gru.weight_ih_l0, enc.gru.weight_hh_l0, enc.gru.bias_ih_l0, enc.gru.bias_hh_l0)]
             cw, cb = [f(c.lin.weight) for c in self.convs], [f(c.bias) for c in self.convs]
-            save = torch.is_grad_enabled() and any(t.requires_grad for t in gw + [Wn, bn] + cw + cb)
+            save = torch.is_grad_enabled() and (edge_w is not None or any(t.requires_grad for t in gw + [Wn, bn] + cw + cb))
             tf = f(tfeat).contiguous() if enc.use_time else None
             out_t = torch.ops.leakgnn.encoder_trunk(
                 f(residual), tf, *gw, Wn, bn, cw, cb, slot, sensor_idx, slot_live, g.nodetab, g.pairs, g.nodetab_t,
                 g.pairs_t, mk.nodetab_s, mk.pairs_s, mk.pos_slot_t, float(self.dropout.p) if drop else 0.0,
-                library.seed_tensor(residual.device) if drop else _NO_SEED, save, bf16=bf16)
+                library.seed_tensor(residual.device) if drop else _NO_SEED, save, edge_w,
+                g.rowptr if edge_w is not None else None, g.col if edge_w is not None else None, bf16=bf16)
             nl = len(self.convs)
             xs = [out_t[nl + 1]] + list(out_t[:nl])  # [x_0 (its sensor rows), x_1 .. x_L]
             x0bits = out_t[nl + 2]
@@ -305,7 +433,7 @@ class LeakDetector(nn.Module):
                 g.col_t, g.w_t, float(self.dropout.p) if drop else 0.0, nm,
                 library.seed_tensor(residual.device) if drop else _NO_SEED,
                 mk.nodetab_s if mk is not None else None, mk.pairs_s if mk is not None else None,
-                mk.pos_slot_t if mk is not None else None, bf16=bf16)
+                mk.pos_slot_t if mk is not None else None, edge_w, bf16=bf16)
             xs = out_t[:-2]                     # [x_0 .. x_L] (then x_L's mask bits and x_0's, when compressed)
             x0bits = out_t[-1]
         h_nodes = xs[-1]                                                   # (N, B, D) node-major, else (B, N, D)
@@ -331,3 +459,26 @@ class LeakDetector(nn.Module):
 
 
 _NO_SEED = torch.zeros(1, dtype=torch.long)  # seed argument of an op that draws no dropout mask
+
+
+def detector_from_args(inp_path: str | Path, sensor_ids: Sequence[str], pipe_ids_in_order: Sequence[str],
+                       args: Optional[dict] = None, cls=None, **kwargs) -> LeakDetector:
+    """The LeakDetector of the training CLI (train_detector.py:250-254 of the reference: widths 64,
+    two layers, dropout 0.1), its edge-weight options read from `args`: the CLI's vars(namespace)
+    or a checkpoint's ckpt["args"].  "edge_weight" in {none, ones, length, inv_length, conductance}
+    (utils.link_edge_weights) and "learn_edge_weight"; a missing key is the unweighted detector.
+    cls: the class to build (the caller's own LeakDetector name; default: this module's)."""
+    args = args or {}
+    mode = args.get("edge_weight") or "none"
+    ew = link_edge_weights(inp_path, mode=mode) if mode != "none" else None
+    return (cls or LeakDetector)(inp_path, sensor_ids, pipe_ids_in_order, sensor_hidden=64, node_hidden=64,
+                                 gnn_layers=2, dropout=0.1, use_time=True, edge_weight=ew,
+                                 learn_edge_weight=bool(args.get("learn_edge_weight", False)), **kwargs)
+
+
+def detector_from_checkpoint(ckpt: dict, inp_path: str | Path, **kwargs) -> LeakDetector:
+    """The detector a checkpoint of train_detector describes, its state loaded strictly (a weighted
+    checkpoint carries `edge_weight` or `edge_log_weight`, which ckpt["args"] announces)."""
+    det = detector_from_args(inp_path, ckpt["sensor_ids"], ckpt["pipe_ids_in_order"], ckpt.get("args"), **kwargs)
+    det.load_state_dict(ckpt["detector_state"], strict=True)
+    return det

@@ -360,7 +360,7 @@ def evaluate_dataset_event_level(
 
 def main() -> None:
     """CLI with the reference's flags (`event_evaluator.py:574-626`)."""
-    from .detector import LeakDetector
+    from .detector import detector_from_checkpoint
     from .predictor import NormalPredictorGRU, NormalPredictorTCN
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset_root", type=str, required=True)
@@ -394,9 +394,7 @@ def main() -> None:
     predictor = pred_cls(num_sensors=S, time_dim=9)
     predictor.load_state_dict(pck["model_state"])
     predictor.to(device).eval()
-    detector = LeakDetector(args.inp_path, dck["sensor_ids"], dck["pipe_ids_in_order"], sensor_hidden=64,
-                            node_hidden=64, gnn_layers=2, dropout=0.1, use_time=True)
-    detector.load_state_dict(dck["detector_state"])
+    detector = detector_from_checkpoint(dck, args.inp_path)  # edge-weight options from dck["args"]
     detector.to(device).eval()
     if list(pck["sensor_ids"]) != list(dck["sensor_ids"]):
         raise ValueError("predictor and detector checkpoints disagree on sensor_ids")

@@ -9,6 +9,7 @@ ordinary ops (fake / meta implementations give output shapes without running ker
   leakgnn::spmm_cols           the propagate of GCNConv's general path (any width)
   leakgnn::gcn_edge_norm       PyG gcn_norm with edge_weight over a built structure (w, w_t, dis)
   leakgnn::sddmm_cols          dL/dw of a propagate (no autograd of its own)
+  sddmm_nm (plain function)    dL/dw of one node-major trunk layer (lg_sddmm_nm)
   leakgnn::mean_pool           PyG global_mean_pool over B equal windows (detector.py:215)
   leakgnn::sensor_proj         sensor_to_node on the sensor rows (detector.py:184-189)
   leakgnn::gru_encoder         SharedSensorGRUEncoder's GRU (detector.py:60-73)
@@ -233,6 +234,36 @@ def sddmm_cols(rowptr: Tensor, col: Tensor, a: Tensor, b: Tensor) -> Tensor:
 @sddmm_cols.register_fake
 def _(rowptr, col, a, b):
     return a.new_empty(col.shape[0])
+
+
+def sddmm_nm(rowptr: Tensor, col: Tensor, dy: Tensor, weight: Tensor, x: Tensor, *, y: Optional[Tensor] = None,
+             ymask: Optional[Tensor] = None, mask_in: bool = False, scale: float = 1.0,
+             ws: Optional[Tensor] = None) -> Tensor:
+    """dL/dw of one node-major trunk layer (lg_sddmm_nm): G[k] = sum_b (dz W)[n, b] . x[col k, b] for
+    every slot k of row n of the forward CSR, dz = dy * scale * [y > 0] under mask_in (the mask
+    from y, or from the bit words ymask of lg_gcn_fwd_nm_bits), else dy.  dy, x, y: (N, B, D).
+    G has col's length, zero past rowptr[N].  Deterministic.  ws: the caller's workspace (uint8),
+    allocated here when None.  A plain function with no autograd of its own, as sddmm_cols: it is
+    what the trunk ops' backward returns as the gradient of edge_w."""
+    lib = load_library()
+    dy, weight, x, y = _c(dy), _c(weight), _c(x), _c(y)
+    _req(dy, weight, x, y)
+    N, B, D = dy.shape
+    _check_d(D)
+    if x.shape != dy.shape or tuple(weight.shape) != (D, D) or rowptr.numel() != N + 1:
+        raise ValueError(f"sddmm_nm: dy {tuple(dy.shape)}, x {tuple(x.shape)}, weight {tuple(weight.shape)}, "
+                         f"rowptr {tuple(rowptr.shape)}")
+    if mask_in and y is None and ymask is None:
+        raise ValueError("sddmm_nm: mask_in needs y or ymask")
+    cap = col.numel()
+    if ws is None:
+        ws = torch.empty(int(lib.lg_sddmm_nm_workspace_bytes(B, cap)), device=dy.device, dtype=torch.uint8)
+    G = torch.empty(cap, device=dy.device, dtype=torch.float32)
+    with _timed("sddmm_nm", dy.device):
+        check(lib.lg_sddmm_nm(ptr(rowptr), ptr(col), ptr(dy), ptr(y), ptr(ymask), ptr(weight), ptr(x), ptr(G), B, N, D,
+                              cap, nat.LG_F_MASK_IN if mask_in else 0, scale, ptr(ws), ws.numel(), stream_of(dy)),
+              "lg_sddmm_nm")
+    return G
 
 
 @torch.library.custom_op(f"{NS}::gcn_edge_norm", mutates_args=(), device_types="cuda")
@@ -1062,7 +1093,7 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
               nodetab: Tensor, pairs: Tensor, rowptr: Tensor, col: Tensor, w: Tensor, nodetab_t: Tensor,
               pairs_t: Tensor, rowptr_t: Tensor, col_t: Tensor, w_t: Tensor, p: float, node_major: bool, seed: Tensor,
               nodetab_s: Optional[Tensor], pairs_s: Optional[Tensor], pos_slot_t: Optional[Tensor],
-              *, bf16: bool = False) -> List[Tensor]:
+              edge_w: Optional[Tensor] = None, *, bf16: bool = False) -> List[Tensor]:
     """[x_0, ..., x_L, ymask, x0bits]: sensor_to_node + node init (detector.py:160, 178-190),
     then L x dropout(relu(GCNConv)).
 
@@ -1079,7 +1110,11 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
     nodetab_s, pairs_s, pos_slot_t (ops.SensorMarks; node-major, L >= 1): x_0 stays
     compressed (lg_node_init_bits_fwd): the returned x_0 is its sensor rows (S, B, D), x0bits
     [x_0 > 0] of every row (int16, ymask's layout), and layer 0 reads them through the marked
-    table (lg_gcn_fwd_nm_x0: the dense forward up to the order of its sums).  Otherwise x0bits is empty."""
+    table (lg_gcn_fwd_nm_x0: the dense forward up to the order of its sums).  Otherwise x0bits is empty.
+    edge_w: the graph's normalised coefficients `w` carrying an autograd edge (learned edge
+    weights, leakgnn::gcn_edge_norm), or None.  An autograd anchor only: the kernels read the
+    tables, which hold the same numbers; when it requires grad the backward returns dL/dw
+    (_layer_dw: lg_sddmm_nm per layer)."""
     lib = load_library()
     h_s, proj_weight, node_bias = _c(h_s), _c(proj_weight), _c(node_bias)
     weights, biases = [_c(t) for t in weights], [_c(t) for t in biases]
@@ -1139,8 +1174,8 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
 
 @gnn_trunk.register_fake
 def _(h_s, proj_weight, node_bias, weights, biases, sensor_slot, sensor_idx, nonsensor_idx, slot_live, nodetab, pairs,
-      rowptr, col, w, nodetab_t, pairs_t, rowptr_t, col_t, w_t, p, node_major, seed, nodetab_s, pairs_s, pos_slot_t, *,
-      bf16=False):
+      rowptr, col, w, nodetab_t, pairs_t, rowptr_t, col_t, w_t, p, node_major, seed, nodetab_s, pairs_s, pos_slot_t,
+      edge_w=None, *, bf16=False):
     B, S = h_s.shape[0], h_s.shape[1]
     D = proj_weight.shape[0]
     N = sensor_slot.shape[0]
@@ -1159,15 +1194,17 @@ def gnn_trunk_backward(grad_out: Tensor, xs: List[Tensor], ymask: Tensor, h_s: T
                        sensor_slot: Tensor, sensor_idx: Tensor, nonsensor_idx: Tensor, slot_live: Optional[Tensor],
                        nodetab_t: Tensor, pairs_t: Tensor, rowptr_t: Tensor, col_t: Tensor, w_t: Tensor, p: float,
                        node_major: bool, x0bits: Optional[Tensor], x0_bias: Optional[Tensor],
-                       pos_slot_t: Optional[Tensor], *, bf16: bool = False
-                       ) -> Tuple[Tensor, Tensor, Tensor, List[Tensor], List[Tensor]]:
-    """(dh_s, dproj_weight, dnode_bias, [dW_l], [db_l]): one fused lg_gcn_bwd[_nm] per layer,
+                       pos_slot_t: Optional[Tensor], rowptr: Optional[Tensor] = None, col: Optional[Tensor] = None,
+                       *, bf16: bool = False
+                       ) -> Tuple[Tensor, Tensor, Tensor, List[Tensor], List[Tensor], Tensor]:
+    """(dh_s, dproj_weight, dnode_bias, [dW_l], [db_l], dw): one fused lg_gcn_bwd[_nm] per layer,
     last first (ReLU/dropout masks of a layer's output and input applied inside the kernel
     from the saved activations; the non-sensor rows' node-bias gradient summed inside layer
     0's launch), then ONE lg_sensor_proj_bwd for the projection (gather of the sensor rows,
     dh_s, dW and the full bias gradient).  x0bits, x0_bias (the node init's bias), pos_slot_t: x_0 is
     compressed (gnn_trunk's x0marks path; xs[0] its sensor rows) and layer 0's backward reads
-    it through lg_gcn_bwd_nm_x0."""
+    it through lg_gcn_bwd_nm_x0.  rowptr, col (the FORWARD CSR): the edge coefficients learn, and
+    dw is dL/dw over its slots (sum over the layers of _layer_dw); otherwise dw is empty."""
     lib = load_library()
     L = len(weights)
     dev = grad_out.device
@@ -1179,6 +1216,7 @@ def gnn_trunk_backward(grad_out: Tensor, xs: List[Tensor], ymask: Tensor, h_s: T
     S, Ds = h_s.shape[1], h_s.shape[2]
     scale = 1.0 / (1.0 - p) if p > 0.0 else 1.0
     dy = grad_out.contiguous()
+    wgrad = _WGrad(rowptr, col) if rowptr is not None else None
     wsb = lib.lg_gcn_bwd_nm_workspace_bytes(D) if node_major else lib.lg_gcn_bwd_workspace_bytes(D)
     # one workspace per layer: the layers' slab reductions run together at the batch flush
     wss = [torch.empty(int(wsb), device=dev, dtype=torch.uint8) for _ in range(L)]
@@ -1189,15 +1227,16 @@ def gnn_trunk_backward(grad_out: Tensor, xs: List[Tensor], ymask: Tensor, h_s: T
         dh_s, dWp, dbp = _trunk_backward_launches(lib, dy, xs, ymask, h_s, proj_weight, weights, sensor_slot, sensor_idx,
                                                   nonsensor_idx, slot_live, nodetab_t, pairs_t, rowptr_t, col_t, w_t,
                                                   node_major, bf16, scale, wss, dWs, dbs, dbias_ns, st,
-                                                  (x0bits, x0_bias, pos_slot_t) if x0bits is not None else None, p)
-    return dh_s, dWp, dbp, dWs, dbs
+                                                  (x0bits, x0_bias, pos_slot_t) if x0bits is not None else None, p,
+                                                  wgrad)
+    return dh_s, dWp, dbp, dWs, dbs, (wgrad.total(dev) if wgrad is not None else torch.empty(0, device=dev))
 
 
 def _trunk_backward_launches(lib, dy, xs, ymask, h_s, proj_weight, weights, sensor_slot, sensor_idx, nonsensor_idx, slot_live,
                              nodetab_t, pairs_t, rowptr_t, col_t, w_t, node_major, bf16, scale, wss, dWs, dbs, dbias_ns,
-                             st, x0c=None, p=0.0):
+                             st, x0c=None, p=0.0, wgrad=None):
     dy = _trunk_layer_launches(lib, dy, xs, ymask, weights, sensor_slot, nodetab_t, pairs_t, rowptr_t, col_t, w_t,
-                               node_major, bf16, scale, wss, dWs, dbs, dbias_ns, st, x0c, p)
+                               node_major, bf16, scale, wss, dWs, dbs, dbias_ns, st, x0c, p, wgrad)
     L = len(weights)
     dev = dy.device
     if node_major:
@@ -1221,11 +1260,53 @@ def _trunk_backward_launches(lib, dy, xs, ymask, h_s, proj_weight, weights, sens
     return dh_s, dWp, dbp
 
 
+class _WGrad:
+    """dL/dw of the trunk's layers, collected by _trunk_layer_launches when the edge coefficients
+    learn: G = sum over the layers of _layer_dw, added in the order the backward visits them
+    (last layer first), over the slots of the forward CSR (rowptr, col)."""
+
+    def __init__(self, rowptr: Tensor, col: Tensor):
+        self.rowptr, self.col, self.G = rowptr, col, None
+
+    def add(self, G: Tensor) -> None:
+        self.G = G if self.G is None else self.G + G
+
+    def total(self, dev) -> Tensor:
+        return self.G if self.G is not None else torch.zeros(self.col.numel(), device=dev)
+
+
+def _layer_dw(dy: Tensor, xs, ymask: Tensor, W: Tensor, l: int, L: int, node_major: bool, scale: float,
+              rowptr: Tensor, col: Tensor, x0c, sensor_slot: Tensor, p: float) -> Tensor:
+    """Layer l's share of dL/dw: G_l[k] = sum_b (dz W_l)[n, b] . x_l[col k, b] for every slot k of
+    row n, with dz = dy * scale * [x_{l+1} > 0] on the last layer and dz = dy on the others (their dy
+    is the layer above's dx, which that launch already masked: LG_F_MASK_OUT), exactly the dz of
+    the layer's own backward launch.  Node-major: lg_sddmm_nm (the last layer's mask from the bit
+    words when the forward wrote them); the compressed node init is materialised for layer 0
+    (lg_node_init_expand; a compressed-x0 form of the kernel is left for later).  Window-major:
+    da on a library GEMM, then ONE lg_sddmm_cols over the [N][B * D] transposes.  Deterministic."""
+    last = l == L - 1
+    if node_major:
+        x = xs[l]
+        if x0c is not None and l == 0:
+            x0bits, node_bias, _ = x0c
+            x = expand_x0(xs[0], x0bits, sensor_slot, node_bias, dy.shape[0], p)
+        bits = ymask if (last and ymask.numel() > 0) else None
+        return sddmm_nm(rowptr, col, dy, W, x, y=xs[l + 1] if (last and bits is None) else None, ymask=bits,
+                        mask_in=last, scale=scale)
+    B, N, D = dy.shape
+    dz = dy * (xs[l + 1] > 0) * scale if last else dy
+    with torch.autocast("cuda", enabled=False):
+        da = (dz.reshape(B * N, D) @ W).view(B, N, D)
+    return torch.ops.leakgnn.sddmm_cols(rowptr, col, da.transpose(0, 1).reshape(N, B * D),
+                                        xs[l].transpose(0, 1).reshape(N, B * D))
+
+
 def _trunk_layer_launches(lib, dy, xs, ymask, weights, sensor_slot, nodetab_t, pairs_t, rowptr_t, col_t, w_t, node_major,
-                          bf16, scale, wss, dWs, dbs, dbias_ns, st, x0c=None, p=0.0) -> Tensor:
+                          bf16, scale, wss, dWs, dbs, dbias_ns, st, x0c=None, p=0.0, wgrad=None) -> Tensor:
     """The GCN layers' backward, last first; returns the node init's pre-activation gradient
     (layer 0's dx: masked by the node init's ReLU / dropout; node-major with the compressed
-    node init: the sensor nodes' rows only) and leaves the non-sensor rows' sum in dbias_ns."""
+    node init: the sensor nodes' rows only) and leaves the non-sensor rows' sum in dbias_ns.
+    wgrad (_WGrad): every layer also adds its dL/dw (_layer_dw)."""
     L = len(weights)
     dev = dy.device
     if node_major:
@@ -1243,6 +1324,9 @@ def _trunk_layer_launches(lib, dy, xs, ymask, weights, sensor_slot, nodetab_t, p
         dW = torch.empty(D, D, device=dev, dtype=torch.float32)
         db = torch.empty(D, device=dev, dtype=torch.float32)
         slot_p, dbias_p = (ptr(sensor_slot), ptr(dbias_ns)) if l == 0 else (None, None)
+        if wgrad is not None:
+            wgrad.add(_layer_dw(dy, xs, ymask, weights[l], l, L, node_major, scale, wgrad.rowptr, wgrad.col, x0c,
+                                sensor_slot, p))
         with _timed("gcn_bwd" if l == L - 1 else f"gcn_bwd_l{l}", dev):
             if x0c is not None and l == 0:  # the compressed node init (xs[0]: its sensor rows, (S, B, D))
                 x0bits, node_bias, pos_slot_t = x0c
@@ -1267,16 +1351,24 @@ def _trunk_layer_launches(lib, dy, xs, ymask, weights, sensor_slot, nodetab_t, p
 
 @gnn_trunk_backward.register_fake
 def _(grad_out, xs, ymask, h_s, proj_weight, weights, sensor_slot, sensor_idx, nonsensor_idx, slot_live, nodetab_t,
-      pairs_t, rowptr_t, col_t, w_t, p, node_major, x0bits, x0_bias, pos_slot_t, *, bf16=False):
+      pairs_t, rowptr_t, col_t, w_t, p, node_major, x0bits, x0_bias, pos_slot_t, rowptr=None, col=None, *, bf16=False):
     D = proj_weight.shape[0]
     return (torch.empty_like(h_s), torch.empty_like(proj_weight), grad_out.new_empty(D),
-            [torch.empty_like(t) for t in weights], [grad_out.new_empty(D) for _ in weights])
+            [torch.empty_like(t) for t in weights], [grad_out.new_empty(D) for _ in weights],
+            grad_out.new_empty(col.shape[0] if col is not None else 0))
 
 
 def _trunk_setup(ctx, inputs, keyword_only_inputs, output):
-    (h_s, proj_weight, node_bias, weights, biases, sensor_slot, sensor_idx, nonsensor_idx, slot_live, _, _, _, _, _,
-     nodetab_t, pairs_t, rowptr_t, col_t, w_t, p, node_major, _, _, _, pos_slot_in) = inputs
+    (h_s, proj_weight, node_bias, weights, biases, sensor_slot, sensor_idx, nonsensor_idx, slot_live, _, _, rowptr, col,
+     _, nodetab_t, pairs_t, rowptr_t, col_t, w_t, p, node_major, _, _, _, pos_slot_in, edge_w) = inputs
     bf16 = bool(keyword_only_inputs.get("bf16", False))
+    # learned edge weights (requires_grad, not needs_input_grad: that tuple is flat over the tensor lists here)
+    ctx.w_grad = edge_w is not None and edge_w.requires_grad
+    # the dispatcher drops trailing arguments that equal their defaults before autograd sees
+    # them, and the backward returns one entry per argument it saw
+    ctx.n_in = 26 if edge_w is not None else 25
+    if ctx.w_grad and bf16:
+        raise NotImplementedError("gnn_trunk: the gradient of edge_w exists on the fp32 tier only")
     ctx.L = len(weights)
     ctx.bf16 = bf16
     ctx.x0c = output[ctx.L + 2].numel() > 0  # x_0 compressed (x0bits non-empty)
@@ -1287,7 +1379,7 @@ def _trunk_setup(ctx, inputs, keyword_only_inputs, output):
     pos_slot_t = pos_slot_in if ctx.x0c else sensor_slot
     ctx.save_for_backward(*output, h_s, proj_weight, *weights, sensor_slot, sensor_idx, nonsensor_idx,
                           slot_live if slot_live is not None else sensor_slot, nodetab_t, pairs_t, rowptr_t, col_t, w_t,
-                          node_bias, pos_slot_t)
+                          node_bias, pos_slot_t, *((rowptr, col) if ctx.w_grad else ()))
 
 
 def _trunk_bwd(ctx, grads):
@@ -1296,15 +1388,16 @@ def _trunk_bwd(ctx, grads):
     xs, ymask, x0bits, h_s, proj_weight = list(saved[:L + 1]), saved[L + 1], saved[L + 2], saved[L + 3], saved[L + 4]
     weights = list(saved[L + 5:2 * L + 5])
     (sensor_slot, sensor_idx, nonsensor_idx, live, nodetab_t, pairs_t, rowptr_t, col_t, w_t, node_bias,
-     pos_slot_t) = saved[2 * L + 5:]
+     pos_slot_t) = saved[2 * L + 5:2 * L + 16]
+    rowptr, col = saved[2 * L + 16:] if ctx.w_grad else (None, None)
     g = grads[L]
     if g is None:
-        return (None,) * 25
-    dh_s, dWp, dbp, dWs, dbs = torch.ops.leakgnn.gnn_trunk_backward(
+        return (None,) * ctx.n_in
+    dh_s, dWp, dbp, dWs, dbs, dw = torch.ops.leakgnn.gnn_trunk_backward(
         g, xs, ymask, h_s, proj_weight, weights, sensor_slot, sensor_idx, nonsensor_idx, live if ctx.has_live else None,
         nodetab_t, pairs_t, rowptr_t, col_t, w_t, ctx.p, ctx.node_major, x0bits if ctx.x0c else None,
-        node_bias if ctx.x0c else None, pos_slot_t if ctx.x0c else None, bf16=ctx.bf16)
-    return (dh_s, dWp, dbp, dWs, dbs) + (None,) * 20
+        node_bias if ctx.x0c else None, pos_slot_t if ctx.x0c else None, rowptr, col, bf16=ctx.bf16)
+    return ((dh_s, dWp, dbp, dWs, dbs) + (None,) * 20 + (dw if ctx.w_grad else None,))[:ctx.n_in]
 
 
 gnn_trunk.register_autograd(_trunk_bwd, setup_context=_trunk_setup)
@@ -1337,13 +1430,15 @@ def encoder_trunk(residual: Tensor, tfeat: Optional[Tensor], w_ih: Tensor, w_hh:
                   proj_weight: Tensor, node_bias: Tensor, weights: List[Tensor], biases: List[Tensor],
                   sensor_slot: Tensor, sensor_idx: Tensor, slot_live: Optional[Tensor], nodetab: Tensor, pairs: Tensor,
                   nodetab_t: Tensor, pairs_t: Tensor, nodetab_s: Tensor, pairs_s: Tensor, pos_slot_t: Tensor, p: float,
-                  seed: Tensor, save: bool, *, bf16: bool = False) -> List[Tensor]:
+                  seed: Tensor, save: bool, edge_w: Optional[Tensor] = None, rowptr: Optional[Tensor] = None,
+                  col: Optional[Tensor] = None, *, bf16: bool = False) -> List[Tensor]:
     """[x_1, ..., x_L, ymask, xs0, x0bits, h_seq, gates]: SharedSensorGRUEncoder (detector.py:60-73),
     the node init (:179-190: h0, the mask column, sensor_to_node, ReLU, dropout) and L x
     dropout(relu(GCNConv)) (:198-201) on the node-major layout [N][B][D].  x_0 stays
     compressed: xs0 (S, B, D) its sensor rows, x0bits [x_0 > 0] of the other rows.  ymask: x_L's
     [x > 0] bits.  h_seq / gates: the GRU's saved steps (empty unless save).  residual and tfeat
-    are data (no gradient)."""
+    are data (no gradient).  edge_w: gnn_trunk's autograd anchor of learned edge coefficients,
+    with the forward CSR rowptr / col its backward walks (all three None otherwise)."""
     lib = load_library()
     residual, tfeat = _c(residual), _c(tfeat)
     w_ih, w_hh, b_ih, b_hh, proj_weight, node_bias = (_c(t) for t in (w_ih, w_hh, b_ih, b_hh, proj_weight, node_bias))
@@ -1400,7 +1495,8 @@ def encoder_trunk(residual: Tensor, tfeat: Optional[Tensor], w_ih: Tensor, w_hh:
 
 @encoder_trunk.register_fake
 def _(residual, tfeat, w_ih, w_hh, b_ih, b_hh, proj_weight, node_bias, weights, biases, sensor_slot, sensor_idx,
-      slot_live, nodetab, pairs, nodetab_t, pairs_t, nodetab_s, pairs_s, pos_slot_t, p, seed, save, *, bf16=False):
+      slot_live, nodetab, pairs, nodetab_t, pairs_t, nodetab_s, pairs_s, pos_slot_t, p, seed, save, edge_w=None,
+      rowptr=None, col=None, *, bf16=False):
     B, Lw, S = residual.shape
     H = w_hh.shape[1]
     D = proj_weight.shape[0]
@@ -1418,10 +1514,12 @@ def encoder_trunk_backward(grad_out: Tensor, xs: List[Tensor], ymask: Tensor, x0
                            tfeat: Optional[Tensor], w_ih: Tensor, w_hh: Tensor, h_seq: Tensor, gates: Tensor,
                            proj_weight: Tensor, node_bias: Tensor, weights: List[Tensor], sensor_slot: Tensor,
                            sensor_idx: Tensor, slot_live: Optional[Tensor], nodetab_t: Tensor, pairs_t: Tensor,
-                           pos_slot_t: Tensor, p: float, *, bf16: bool = False) -> List[Tensor]:
-    """[dw_ih, dw_hh, db_ih, db_hh, dproj_weight, dnode_bias, dW_0 .. dW_{L-1}, db_0 .. db_{L-1}]: the
+                           pos_slot_t: Tensor, p: float, rowptr: Optional[Tensor] = None,
+                           col: Optional[Tensor] = None, *, bf16: bool = False) -> List[Tensor]:
+    """[dw_ih, dw_hh, db_ih, db_hh, dproj_weight, dnode_bias, dW_0 .. dW_{L-1}, db_0 .. db_{L-1}, dw]: the
     layers' backward (last first; layer 0 on the compressed x_0, its dx for the sensor rows
-    only), then lg_gru_node_init_bwd; one reduce batch for all of them."""
+    only), then lg_gru_node_init_bwd; one reduce batch for all of them.  rowptr, col (the
+    forward CSR): dw = dL/dw of the edge coefficients as in gnn_trunk_backward, else empty."""
     lib = load_library()
     if h_seq.numel() == 0 or gates.numel() == 0:
         raise RuntimeError("encoder_trunk was run with save=False; no backward")
@@ -1441,34 +1539,44 @@ def encoder_trunk_backward(grad_out: Tensor, xs: List[Tensor], ymask: Tensor, x0
     db_ih, db_hh = torch.empty(3 * H, device=dev), torch.empty(3 * H, device=dev)
     dWp, dbp = torch.empty_like(proj_weight), torch.empty(D, device=dev)
     wsg = torch.empty(int(lib.lg_gru_node_init_bwd_workspace_bytes(B, S, I, H)), device=dev, dtype=torch.uint8)
+    wgrad = _WGrad(rowptr, col) if rowptr is not None else None
     with _reduce_batch(lib, st):
         dx0 = _trunk_layer_launches(lib, grad_out.contiguous(), xs, ymask, weights, sensor_slot, nodetab_t, pairs_t,
                                     None, None, None, True, bf16, scale, wss, dWs, dbs, dbias_ns, st,
-                                    (x0bits, node_bias, pos_slot_t), p)
+                                    (x0bits, node_bias, pos_slot_t), p, wgrad)
         with _timed("gru_bwd", dev):
             check(lib.lg_gru_node_init_bwd(ptr(residual), ptr(tfeat), ptr(w_ih), ptr(w_hh), ptr(h_seq), ptr(gates),
                                            ptr(dx0), ptr(sensor_idx), ptr(slot_live) if slot_live is not None else None,
                                            ptr(proj_weight), ptr(dbias_ns), ptr(dw_ih), ptr(dw_hh), ptr(db_ih),
                                            ptr(db_hh), ptr(dWp), ptr(dbp), B, Lw, S, I, H, N, ptr(wsg), wsg.numel(),
                                            st), "lg_gru_node_init_bwd")
-    return [dw_ih, dw_hh, db_ih, db_hh, dWp, dbp] + dWs + dbs
+    return ([dw_ih, dw_hh, db_ih, db_hh, dWp, dbp] + dWs + dbs
+            + [wgrad.total(dev) if wgrad is not None else torch.empty(0, device=dev)])
 
 
 @encoder_trunk_backward.register_fake
 def _(grad_out, xs, ymask, x0bits, residual, tfeat, w_ih, w_hh, h_seq, gates, proj_weight, node_bias, weights,
-      sensor_slot, sensor_idx, slot_live, nodetab_t, pairs_t, pos_slot_t, p, *, bf16=False):
+      sensor_slot, sensor_idx, slot_live, nodetab_t, pairs_t, pos_slot_t, p, rowptr=None, col=None, *, bf16=False):
     H = w_hh.shape[1]
     D = proj_weight.shape[0]
     return ([torch.empty_like(w_ih), torch.empty_like(w_hh), w_ih.new_empty(3 * H), w_ih.new_empty(3 * H),
              torch.empty_like(proj_weight), proj_weight.new_empty(D)] + [torch.empty_like(t) for t in weights]
-            + [proj_weight.new_empty(D) for _ in weights])
+            + [proj_weight.new_empty(D) for _ in weights]
+            + [proj_weight.new_empty(col.shape[0] if col is not None else 0)])
 
 
 def _et_setup(ctx, inputs, keyword_only_inputs, output):
     (residual, tfeat, w_ih, w_hh, b_ih, b_hh, proj_weight, node_bias, weights, biases, sensor_slot, sensor_idx,
-     slot_live, nodetab, pairs, nodetab_t, pairs_t, nodetab_s, pairs_s, pos_slot_t, p, seed, save) = inputs
+     slot_live, nodetab, pairs, nodetab_t, pairs_t, nodetab_s, pairs_s, pos_slot_t, p, seed, save, edge_w, rowptr,
+     col) = inputs
     L = len(weights)
     ctx.L, ctx.p, ctx.bf16 = L, p, bool(keyword_only_inputs.get("bf16", False))
+    ctx.w_grad = edge_w is not None and edge_w.requires_grad  # learned edge weights (as gnn_trunk)
+    # trailing arguments equal to their defaults never reach autograd (see _trunk_setup)
+    ctx.n_in = 26 - (3 if (edge_w is None and rowptr is None and col is None) else
+                     2 if (rowptr is None and col is None) else 1 if col is None else 0)
+    if ctx.w_grad and (ctx.bf16 or rowptr is None or col is None):
+        raise NotImplementedError("encoder_trunk: the gradient of edge_w needs rowptr / col and the fp32 tier")
     ctx.has_tfeat, ctx.has_live = tfeat is not None, slot_live is not None
     # x_1 .. x_{L-1}, ymask, xs0, x0bits, h_seq, gates: saved, never differentiated
     ctx.mark_non_differentiable(*output[:L - 1], *output[L:])
@@ -1476,27 +1584,29 @@ def _et_setup(ctx, inputs, keyword_only_inputs, output):
     ctx.save_for_backward(*output[:L], output[L], output[L + 1], output[L + 2], output[L + 3], output[L + 4],
                           residual, tfeat if tfeat is not None else residual, w_ih, w_hh, proj_weight, node_bias,
                           *weights, sensor_slot, sensor_idx, slot_live if slot_live is not None else sensor_slot,
-                          nodetab_t, pairs_t, pos_slot_t)
+                          nodetab_t, pairs_t, pos_slot_t, *((rowptr, col) if ctx.w_grad else ()))
 
 
 def _et_bwd(ctx, grads):
     L = ctx.L
     g = grads[L - 1]
     if g is None:
-        return (None,) * 23
+        return (None,) * ctx.n_in
     sv = ctx.saved_tensors
     xl = list(sv[:L])
     ymask, xs0, x0bits, h_seq, gates = sv[L:L + 5]
     residual, tfeat, w_ih, w_hh, proj_weight, node_bias = sv[L + 5:L + 11]
     weights = list(sv[L + 11:2 * L + 11])
-    sensor_slot, sensor_idx, live, nodetab_t, pairs_t, pos_slot_t = sv[2 * L + 11:]
+    sensor_slot, sensor_idx, live, nodetab_t, pairs_t, pos_slot_t = sv[2 * L + 11:2 * L + 17]
+    rowptr, col = sv[2 * L + 17:] if ctx.w_grad else (None, None)
     out = torch.ops.leakgnn.encoder_trunk_backward(
         g, [xs0] + xl, ymask, x0bits, residual, tfeat if ctx.has_tfeat else None, w_ih, w_hh, h_seq, gates,
         proj_weight, node_bias, weights, sensor_slot, sensor_idx, live if ctx.has_live else None, nodetab_t, pairs_t,
-        pos_slot_t, ctx.p, bf16=ctx.bf16)
+        pos_slot_t, ctx.p, rowptr, col, bf16=ctx.bf16)
     dw_ih, dw_hh, db_ih, db_hh, dWp, dbp = out[:6]
-    dWs, dbs = list(out[6:6 + L]), list(out[6 + L:])
-    return (None, None, dw_ih, dw_hh, db_ih, db_hh, dWp, dbp, dWs, dbs) + (None,) * 13
+    dWs, dbs = list(out[6:6 + L]), list(out[6 + L:6 + 2 * L])
+    return ((None, None, dw_ih, dw_hh, db_ih, db_hh, dWp, dbp, dWs, dbs) + (None,) * 13
+            + (out[6 + 2 * L] if ctx.w_grad else None, None, None))[:ctx.n_in]
 
 
 encoder_trunk.register_autograd(_et_bwd, setup_context=_et_setup)

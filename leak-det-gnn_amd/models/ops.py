@@ -304,6 +304,15 @@ class SensorMarks:
         marks._keepalive = (slot, pos, scratch_t, scratch_p)  # live until the stream has consumed them
         return marks
 
+    def refresh(self, g: GCNGraph) -> None:
+        """The marked forward table and pair array again from g's (after GCNGraph.reweight: they
+        carry the coefficients), IN PLACE into nodetab_s / pairs_s: one launch, no allocation,
+        capturable.  pos_slot_t holds no weight and stays."""
+        slot, pos = self._keepalive[0], self._keepalive[1]
+        check(load_library().lg_nm_table_sensor_mark(ptr(g.nodetab), ptr(g.pairs), g.num_nodes, g.pairs.shape[0],
+                                                     ptr(slot), ptr(self.nodetab_s), ptr(self.pairs_s), ptr(pos),
+                                                     stream_of(slot)), "lg_nm_table_sensor_mark")
+
 
 def schedule_order(edge_index: torch.Tensor, num_nodes: int) -> torch.Tensor:
     """int32 (N,) reverse Cuthill-McKee order of the graph (lg_rcm_order, host)."""

@@ -46,7 +46,7 @@ import torch.nn as nn
 
 from .datasets import AbruptLeakDetectorDataset, SensorStandardizer
 from .ddp import GradAllReduce, dist_env, init_distributed, reseed_rank
-from .detector import LeakDetector
+from .detector import LeakDetector, detector_from_args
 from .loss import CrossEntropyLoss
 from .optim import ClipAdamW
 from .predictor import NormalPredictorGRU, NormalPredictorTCN
@@ -203,6 +203,12 @@ def main(argv=None) -> None:
     ap.add_argument("--capture", type=str, default="auto", choices=["auto", "on", "off"],
                     help="replay each full-size training batch's step as one captured HIP graph "
                          "(models/graph_step.py; auto = on for the GPU path); the tail batch runs eagerly")
+    ap.add_argument("--edge_weight", type=str, default="none",
+                    choices=["none", "ones", "length", "inv_length", "conductance"],
+                    help="per-link edge weights of the GCN trunk from the .inp file (utils.link_edge_weights); "
+                         "none = the unweighted graph")
+    ap.add_argument("--learn_edge_weight", action="store_true",
+                    help="learn the link weights (a parameter edge_log_weight, starting from --edge_weight, or from 1)")
     ap.add_argument("--profile", type=int, default=0,
                     help="torch.profiler over this many training steps (after one warm-up step): "
                          "<out_dir>/detector_trace.json + detector_ops.txt on rank 0 (models/profiling.py)")
@@ -272,9 +278,8 @@ def main(argv=None) -> None:
     _, val_loader = mk(args.val_steps, args.seed + 1, 2048, leak_val, nl_val)
     _, test_loader = mk(args.test_steps, args.seed + 2, 2048, leak_test, nl_test)
 
-    detector = LeakDetector(inp_path=args.inp_path, sensor_node_ids=sensor_ids, pipe_ids_in_order=pipe_ids_in_order,
-                            sensor_hidden=64, node_hidden=64, gnn_layers=2, dropout=0.1, use_time=True,
-                            mlp_dtype=args.dtype).to(device)
+    detector = detector_from_args(args.inp_path, sensor_ids, pipe_ids_in_order, vars(args), cls=LeakDetector,
+                                  mlp_dtype=args.dtype).to(device)
     clip = args.grad_clip if args.grad_clip and args.grad_clip > 0 else None
     fused_step = device.type == "cuda"  # clip_grad_norm_ + AdamW.step as one fused op pair
     if fused_step:
@@ -370,6 +375,7 @@ def main(argv=None) -> None:
                         cstep.inputs[1].copy_(tfeat)
                         cstep.label.copy_(label)
                     loss = cstep()
+                    detector.invalidate_edge_weights()  # the replay's optimizer step moved no _version
                 else:
                     logits = detector(residual, tfeat)
                     loss = loss_fn(logits, label)

@@ -135,6 +135,53 @@ def build_wdn_graph_from_inp(
                     pipe_ends=pipe_ends, edge_index=edge_index)
 
 
+LINK_WEIGHT_MODES = ("ones", "length", "inv_length", "conductance")
+
+
+def link_edge_weights(inp_path: str | Path, include_links: Sequence[str] = ("PIPES", "PUMPS", "VALVES"),
+                      mode: str = "inv_length", eps: float = 0.1) -> Any:
+    """(n_links,) fp32 weights for LeakDetector(edge_weight=...), one per link in the order of the
+    link table build_wdn_graph_from_inp walks (the same sections in the same order, a repeated
+    link id overwriting in place), so link j is the directed edges 2j and 2j + 1 of its
+    edge_index.  mode: "length" (the [PIPES] length column), "inv_length" (1 / length),
+    "conductance" (diameter^2 / length) or "ones".  Pumps and valves take length `eps`, the
+    convention of window_evaluator._parse_links_with_length (as does its fallback of 1.0 for an
+    unreadable length), and the median pipe diameter.  The result is divided by its mean, so the
+    weights are O(1) whatever the unit of the file."""
+    if mode not in LINK_WEIGHT_MODES:
+        raise ValueError(f"mode must be one of {LINK_WEIGHT_MODES}, got {mode!r}")
+    sec = parse_epanet_inp(inp_path)
+    table: Dict[str, Tuple[float, float]] = {}  # id -> (length, diameter or nan), in link-table order
+    for name in include_links:
+        pipes = name.upper() == "PIPES"
+        for ln in sec.get(name.upper(), []):
+            tok = ln.split()
+            if len(tok) < 3:
+                continue
+            length, diam = (1.0 if pipes else float(eps)), float("nan")
+            if pipes:
+                try:
+                    length = float(tok[3])
+                except (IndexError, ValueError):
+                    length = 1.0
+                try:
+                    diam = float(tok[4])
+                except (IndexError, ValueError):
+                    pass
+            table[tok[0]] = (length, diam)
+    if not table:
+        raise ValueError(f"No link endpoints found from sections {tuple(include_links)} in inp file.")
+    length = np.array([v[0] for v in table.values()], dtype=np.float64)
+    diam = np.array([v[1] for v in table.values()], dtype=np.float64)
+    if not np.all(length > 0):
+        raise ValueError("link_edge_weights: every link length must be positive")
+    known = diam[np.isfinite(diam) & (diam > 0)]
+    diam = np.where(np.isfinite(diam) & (diam > 0), diam, np.median(known) if known.size else 1.0)
+    w = {"ones": np.ones_like(length), "length": length, "inv_length": 1.0 / length,
+         "conductance": diam * diam / length}[mode]
+    return torch.from_numpy((w / w.mean()).astype(np.float32))
+
+
 # LEAKGNN_RESIDUAL=stock keeps the per-window module calls (for A/B timing).
 RESIDUAL_FAST_PATH = os.environ.get("LEAKGNN_RESIDUAL", "fast") != "stock"
 
