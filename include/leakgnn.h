@@ -158,6 +158,44 @@ int lg_cross_entropy_bwd(const float* logits, const int64_t* target, const float
                          int64_t B, int64_t C, int64_t ldx, int64_t ignore_index, float* dlogits, int64_t ldd,
                          lg_stream_t stream);
 
+/* The same loss with nn.CrossEntropyLoss's options (added to ABI 26 without a bump: additions
+ * only): class weights, label smoothing, the three reductions, and a smoothing table in place
+ * of torch's uniform one.  weight: w [C] or NULL (all ones).  smoothing: U [C][C] (row stride
+ * ldu >= C) or NULL (every entry 1 / C, torch's label_smoothing); row y is the distribution the
+ * eps mass of a row labelled y is spread over.  eps in [0, 1).  reduction: 0 mean, 1 sum, 2 none.
+ * For a counted row b (y_b != ignore_index and 0 <= y_b < C):
+ *   a_b[c] = w[c] * ((1 - eps) * [c == y_b] + eps * U[y_b][c])
+ *   S_b    = sum_c a_b[c]
+ *   row_b  = S_b * lse_b - sum_c a_b[c] * x[b][c]            ( = -sum_c a_b[c] * log softmax_b[c] )
+ *   mean: loss = sum_b row_b / sum_b w[y_b]     sum: loss = sum_b row_b     none: rowloss[b] = row_b
+ *   dlogits[b][c] = G_b * (S_b * softmax_b[c] - a_b[c]),  G_b = grad[0] / sum_b w[y_b] (mean),
+ *                   grad[0] (sum), grad[b] (none); exactly 0 for rows that are not counted.
+ * A term with a_b[c] == 0 contributes exactly 0, also where x[b][c] = -inf; with a_b[c] > 0 there
+ * the loss is +inf, as torch.  Rows with |lse_b| >= 32 take S_b * log(sum) + sum_c a_b[c] *
+ * (max - x[b][c]) and exp(x - max) / sum, the rule of lg_cross_entropy_fwd.
+ *   fwd: ONE launch.  lse [B], rowsum [B] (S_b) and, for mean and sum, denom (device fp32 scalar,
+ *        sum_b w[y_b]) are saved for the backward; rowloss [B] holds row_b (0 for ignored rows)
+ *        and is the result for none.  mean / sum: the workgroup that finishes last sums the rows
+ *        in row order into loss (device fp32 scalar) and denom and resets counter (as
+ *        lg_cross_entropy_fwd's; the two may share one); none: loss, denom and counter are not
+ *        used and may be NULL.  No float atomics: bit-identical from run to run.
+ *   bwd: ONE launch; grad is a device scalar (mean, sum) or [B] (none); a_b[c] is formed again
+ *        from weight, smoothing and eps, which must be those of the forward.
+ *   A target outside [0, C) other than ignore_index reads nothing (U is indexed by the label),
+ *   gives row_b = NaN (so a NaN mean / sum) and a dlogits row of 0.  B == 0: mean NaN, sum 0,
+ *   denom 0, nothing else written.  No row counted: mean NaN (0 / 0, as torch), sum 0.
+ *   LG_EINVAL, before any HIP call: B < 0, C <= 0, ldx < C, ldd < C, eps outside [0, 1),
+ *   smoothing with ldu < C, reduction outside 0..2, a NULL pointer that the call would use.
+ *   Tested against the fp64 expression in tests/test_gpu_ce_options.py. */
+int lg_cross_entropy_opt_fwd(const float* logits, const int64_t* target, int64_t B, int64_t C, int64_t ldx,
+                             int64_t ignore_index, const float* weight, const float* smoothing, int64_t ldu,
+                             float eps, int reduction, float* loss, float* lse, float* rowloss, float* rowsum,
+                             float* denom, unsigned* counter, lg_stream_t stream);
+int lg_cross_entropy_opt_bwd(const float* logits, const int64_t* target, const float* lse, const float* rowsum,
+                             const float* denom, const float* grad, int64_t B, int64_t C, int64_t ldx,
+                             int64_t ignore_index, const float* weight, const float* smoothing, int64_t ldu,
+                             float eps, int reduction, float* dlogits, int64_t ldd, lg_stream_t stream);
+
 /* Training-step tail: torch.nn.utils.clip_grad_norm_(params, max_norm) then
  * torch.optim.AdamW.step() (reference train_detector.py:313-317), ONE launch (ABI 23; two
  * before), two when the parameters need more 1024-element slices than the device has CUs.

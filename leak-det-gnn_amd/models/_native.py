@@ -143,6 +143,12 @@ SIGNATURES = {
     "lg_head_mse_fwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
     "lg_head_mse_bwd_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "lg_head_mse_bwd": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _i64, _p]),
+    # cross entropy with weights, label smoothing (uniform or a table) and the three reductions
+    # (added to ABI 26 without a bump: additions only)
+    "lg_cross_entropy_opt_fwd": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _p, _p, _i64, _f32, _i32, _p, _p, _p, _p, _p,
+                                        _p, _p]),
+    "lg_cross_entropy_opt_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _i64, _f32, _i32, _p,
+                                        _i64, _p]),
 }
 
 _lib = None

@@ -8,7 +8,8 @@ checkpoint schema (:346-353).
 
 The detector is this package's LeakDetector (HIP GRU / GCN / heads kernels); batches
 come from datasets.DeviceBatchLoader (--loader torch restores the DataLoader path);
-on the GPU the loss is models.loss.CrossEntropyLoss (two launches) and clip_grad_norm_ +
+on the GPU the loss is models.loss.CrossEntropyLoss (two launches; --label_smoothing,
+--smooth_sigma_m and --noleak_weight select its options, loss.loss_from_args) and clip_grad_norm_ +
 AdamW run as models.optim.ClipAdamW (two launches, the same arithmetic as torch's
 clip then AdamW step); on the CPU they are torch's.  Checkpoints load with
 torch.load(weights_only=True).
@@ -47,7 +48,7 @@ import torch.nn as nn
 from .datasets import AbruptLeakDetectorDataset, SensorStandardizer
 from .ddp import GradAllReduce, dist_env, init_distributed, reseed_rank
 from .detector import LeakDetector, detector_from_args
-from .loss import CrossEntropyLoss
+from .loss import check_loss_args, loss_from_args
 from .optim import ClipAdamW
 from .predictor import NormalPredictorGRU, NormalPredictorTCN
 from .train_predictor import make_loader, pick_device, set_seed
@@ -173,7 +174,9 @@ def load_predictor(ckpt_path: str | Path, device: torch.device) -> Tuple[nn.Modu
     return model, ckpt
 
 
-def main(argv=None) -> None:
+def main(argv=None, *, parse_only: bool = False):
+    """Train and evaluate.  parse_only: return the parsed namespace (the CLI's flags and their
+    defaults) without doing anything else."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--leak_root", type=str, required=True, help="Path to leak dataset root")
     ap.add_argument("--inp_path", type=str, required=True, help="Path to EPANET .inp file")
@@ -209,12 +212,22 @@ def main(argv=None) -> None:
                          "none = the unweighted graph")
     ap.add_argument("--learn_edge_weight", action="store_true",
                     help="learn the link weights (a parameter edge_log_weight, starting from --edge_weight, or from 1)")
+    ap.add_argument("--label_smoothing", type=float, default=0.0,
+                    help="label smoothing eps in [0, 1) of the training loss (0: none)")
+    ap.add_argument("--smooth_sigma_m", type=float, default=0.0,
+                    help="with --label_smoothing: spread the eps mass over the pipes by exp(-distance / SIGMA metres) "
+                         "of the network distance the evaluator scores by (loss.distance_smoothing; GPU only); "
+                         "0 = torch's uniform smoothing")
+    ap.add_argument("--noleak_weight", type=float, default=1.0,
+                    help="class weight of the no-leak class in the training loss (pipes keep 1); single process only")
     ap.add_argument("--profile", type=int, default=0,
                     help="torch.profiler over this many training steps (after one warm-up step): "
                          "<out_dir>/detector_trace.json + detector_ops.txt on rank 0 (models/profiling.py)")
     ap.add_argument("--perf_log", type=str, default="detector_perf.jsonl",
                     help="JSONL perf log (windows/s per log interval), relative to --out_dir; '' disables")
     args = ap.parse_args(argv)
+    if parse_only:
+        return args
 
     rank, local_rank, world = dist_env()
     if world > 1:
@@ -231,6 +244,7 @@ def main(argv=None) -> None:
     if world > 1 and device.type == "cuda":
         device = torch.device("cuda", local_rank % max(torch.cuda.device_count(), 1))
         torch.cuda.set_device(device)
+    check_loss_args(args, world, device)
     # one log (rank 0's); every rank runs the same steps
     print = builtins.print if lead else (lambda *a, **k: None)  # noqa: A001
     print(f"{now()} [detector] device={device} seed={args.seed} world={world}")
@@ -286,7 +300,9 @@ def main(argv=None) -> None:
         opt = ClipAdamW(detector.parameters(), lr=args.lr, weight_decay=args.weight_decay, max_norm=clip)
     else:
         opt = torch.optim.AdamW(detector.parameters(), lr=args.lr, weight_decay=args.weight_decay)
-    loss_fn = CrossEntropyLoss()  # torch's own path on the CPU
+    # CrossEntropyLoss() unless --label_smoothing / --smooth_sigma_m / --noleak_weight ask for more;
+    # torch's own path on the CPU
+    loss_fn = loss_from_args(args, args.inp_path, pipe_ids_in_order).to(device)
     allreduce = GradAllReduce(detector.parameters())  # no-op at world 1
     # identical weights on every rank (built above from args.seed); from here on each rank
     # draws its own dropout seeds

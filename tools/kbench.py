@@ -1,7 +1,7 @@
 """Kernel micro-benchmark (GPU): times individual libleakgnn kernels in isolation with
 HIP events on the launch stream.  Used for tuning and under rocprofv3 --pmc.
 
-  python tools/kbench.py [--which gcn_fwd,gcn_bwd,spmm,edge_fwd,edge_bwd,gru_fwd,gru_bwd,gru_ni_fwd,gru_ni_bwd,gru_stack,gru_predictor,tcn,tcn_train,predictor_step] [--B 256] [--iters 50]
+  python tools/kbench.py [--which gcn_fwd,gcn_bwd,spmm,edge_fwd,edge_bwd,gru_fwd,gru_bwd,gru_ni_fwd,gru_ni_bwd,gru_stack,gru_predictor,tcn,tcn_train,predictor_step,ce_options] [--B 256] [--iters 50]
 """
 import argparse
 import ctypes
@@ -1005,6 +1005,81 @@ def main():
             tp.check_optimizer_errors(ob)
             tp.check_optimizer_errors(oc)
             res[f"predictor_step_{arch}"] = leg
+    if "ce_options" in which:
+        # the loss options, forward plus backward, at the detector's (256, 765) logits:
+        #   hip    models.loss.CrossEntropyLoss (leakgnn::cross_entropy_opt: one launch each way)
+        #   torch  torch.nn.CrossEntropyLoss with the same arguments; for the table, which torch does
+        #          not have, -(A * log_softmax(x)).sum() / B with A = 0.9 onehot + 0.1 U[label] formed
+        #          once outside the timed region
+        # each as eager calls and as a replayed HIP graph of the forward and backward (what a captured
+        # step pays), predictor_step's protocol: windows of about --window-ms, the legs alternating
+        # within a round, --rounds rounds, median with min .. max.
+        from models import loss as mloss
+        Bc, C = 256, 765
+        gen = torch.Generator().manual_seed(0)
+        x0 = (torch.randn(Bc, C, generator=gen) * 3).to(dev)
+        lab = torch.randint(0, C, (Bc,), generator=gen).to(dev)
+        wv = torch.ones(C)
+        wv[C - 1] = 0.5
+        U = torch.softmax(torch.randn(C, C, generator=gen, dtype=torch.float64) * 3, dim=1).float()
+        A = (0.9 * torch.nn.functional.one_hot(lab, C).float() + 0.1 * U.to(dev)[lab]).contiguous()
+        cfgs = {"weight": {"weight": wv}, "eps": {"label_smoothing": 0.1},
+                "eps_table": {"label_smoothing": 0.1, "smoothing": U}, "sum": {"reduction": "sum"}}
+
+        def window_us(fn, n):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(n):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) * 1e3 / n
+
+        def legs_of(loss_of):
+            xx = x0.clone().requires_grad_(True)
+
+            def eager():
+                xx.grad = None
+                loss_of(xx).backward()
+            eager()
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                torch.autograd.grad(loss_of(xx), xx)
+            torch.cuda.current_stream().wait_stream(side)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                keep = torch.autograd.grad(loss_of(xx), xx)
+            return {"eager": eager, "graph": graph.replay, "_keep": keep}
+
+        for name, kw in cfgs.items():
+            hip = mloss.CrossEntropyLoss(**kw).to(dev)
+            if "smoothing" in kw:
+                def ref(xx):
+                    return -(A * torch.log_softmax(xx, dim=1)).sum() / Bc
+            else:
+                tmod = torch.nn.CrossEntropyLoss(**kw).to(dev)
+
+                def ref(xx, tmod=tmod):
+                    return tmod(xx, lab)
+            sides = {"hip": legs_of(lambda xx, hip=hip: hip(xx, lab)), "torch": legs_of(ref)}
+            fns = {f"{s}_{m}": sides[s][m] for m in ("eager", "graph") for s in ("hip", "torch")}
+            iters = {}
+            for key, fn in fns.items():
+                for _ in range(3):
+                    fn()
+                torch.cuda.synchronize()
+                iters[key] = max(3, int(args.window_ms * 1e3 / window_us(fn, 10)))
+            samples = {key: [] for key in fns}
+            for _ in range(args.rounds):
+                for key, fn in fns.items():
+                    samples[key].append(window_us(fn, iters[key]))
+            leg = {"rounds": args.rounds, "window_ms": args.window_ms, "B": Bc, "C": C}
+            for key, v in samples.items():
+                leg[key] = {"us": round(float(np.median(v)), 2), "min_max_us": [round(min(v), 2), round(max(v), 2)]}
+            for m in ("eager", "graph"):
+                leg[f"{m}_hip_slowest_beats_torch_fastest"] = max(samples[f"hip_{m}"]) < min(samples[f"torch_{m}"])
+            res[f"ce_options_{name}"] = leg
     for k, v in res.items():
         print(k, json.dumps({a: round(b, 2) if isinstance(b, float) else b for a, b in v.items()}))
 
