@@ -196,6 +196,75 @@ int lg_cross_entropy_opt_bwd(const float* logits, const int64_t* target, const f
                              int64_t ignore_index, const float* weight, const float* smoothing, int64_t ldu,
                              float eps, int reduction, float* dlogits, int64_t ldd, lg_stream_t stream);
 
+/* Evaluator tails (added to ABI 26 without a bump: additions only).  Both work on rows of logits
+ * [.][C] (fp32, row stride ldx >= C) under ONE total order on a row's entries:
+ *   a precedes b  <=>  value(a) > value(b), with NaN counted as greater than +inf (torch's argmax
+ *                      rule) and -0 equal to +0, or the values are equal and index(a) < index(b).
+ * The "first entry" of a row is its argmax with ties (and several NaNs) going to the lowest index;
+ * the "position" of an entry is the number of entries that precede it.  On rows with no repeated
+ * value and no NaN this is what torch's argmax / topk / argsort compute; on ties, where torch's
+ * answer on a GPU is unspecified, it is defined.  C <= 2^31 - 1 (LG_EUNSUPPORTED above).
+ *
+ * lg_window_metrics: the per-batch tail of DetectorEvaluator.evaluate (reference
+ * window_evaluator.py:227-483), ONE launch, one wave per row, each row read once, no sort.
+ *   label  : int64 [B].  nlc: the no-leak class, 1 <= nlc <= C - 1.
+ *   bucket : int32 [B] or NULL: -1 (none), 0 early, 1 late, 2 pre, 3 noleak.
+ *   dist   : fp64 [nlc][nlc] or NULL, dist[y][p] = distance from true pipe y to predicted pipe p.
+ *   inv_rank: int32 [nlc][nlc] or NULL (needs dist), inv_rank[p][y] = position of y among p's
+ *            neighbours by distance.
+ *   radii_host [R], acc_is_host [I]: HOST arrays, R, I in 0 .. LG_WM_MAX_LIST (passed by value to
+ *            the launch).
+ * Per row with 0 <= label < C:
+ *   pred1 = index of the first entry of the row;  hit1 = pred1 == label
+ *   hitk  = position of logits[label] among all C entries < min(topk, C)
+ *   rank  = 1 + position of logits[min(label, nlc - 1)] among the entries with index < nlc
+ *   leak row (label != nlc): missed = pred1 == nlc;  d = missed ? +inf : dist[label][min(pred1, nlc - 1)];
+ *                            pos = inv_rank[min(pred1, nlc - 1)][label]
+ *     (with C > nlc + 1, a leak label > nlc has no table row: d = +inf and no acc_i, nothing is read)
+ * counters: int64 [n_counters], n_counters == LG_WM_COUNTERS, ACCUMULATED in place (the caller
+ * zeroes them once), slots in this order:
+ *    0 total          1 correct1 (hit1)      2 correctk (hitk)     3 nl_total (label == nlc)
+ *    4 nl_correct     5 leak_total           6 leak_correct1       7 leak_correctk
+ *    8 tp  9 fp  10 fn  11 tn                (pred1 != nlc  x  label != nlc)
+ *   12 + 4 k + {0, 1, 2, 3}: b_total, b_correct1, b_correctk, b_pred_nl (pred1 == nlc) of bucket k
+ *   28 pre_false_alarm (label == nlc, pred1 != nlc, bucket 2)       29 noleak_false_alarm (bucket 3)
+ *   30 + r: success[r] = leak row and d <= radii[r]                  (untouched without dist)
+ *   38 + i: acc_i[i] = leak row, !missed, pos < acc_is[i], acc_is[i] > 0   (untouched without inv_rank)
+ *   46 bad_label: a row whose label is outside [0, C) adds here and NOWHERE else; nothing is read
+ *      at its label.
+ * Integer accumulation only (registers, LDS, then 64-bit integer vector atomics): no float
+ * atomics, so the counters do not depend on scheduling and two runs are equal.
+ *   rank_out: int32 [B]: rank, 0 on no-leak (and bad-label) rows.
+ *   atd_out : fp64 [B], written only with dist: d, NaN on no-leak (and bad-label) rows.
+ * LG_EINVAL before any HIP call: B < 0, C < 2, ldx < C, nlc outside 1 .. C - 1, topk < 1, R or I
+ * outside 0 .. LG_WM_MAX_LIST (or positive with a NULL host array), inv_rank without dist, NULL
+ * counters or n_counters != LG_WM_COUNTERS, and, for B > 0, NULL logits, label, rank_out, or
+ * atd_out with dist.  B == 0 returns LG_OK without a launch.
+ * Tested against a brute-force statement of the order in tests/test_gpu_window_metrics.py. */
+#define LG_WM_MAX_LIST 8
+#define LG_WM_COUNTERS 47
+int lg_window_metrics(const float* logits, const int64_t* label, int64_t B, int64_t C, int64_t ldx, int64_t nlc,
+                      int64_t topk, const int32_t* bucket, const double* dist, const int32_t* inv_rank,
+                      const double* radii_host, int R, const int64_t* acc_is_host, int I, int64_t* counters,
+                      int64_t n_counters, int32_t* rank_out, double* atd_out, lg_stream_t stream);
+
+/* lg_event_decide: trigger and aggregation of the event evaluator (reference
+ * event_evaluator.py:327-342) over the logits [W][C] of one scenario's windows; TWO launches,
+ * nothing read back in between.  end_ns: int64 [W], the windows' end times, increasing.
+ *   out[0] trig = first row whose first entry (the order above) is not `noleak`; -1 if none
+ *   out[1] stop = first i >= trig with end_ns[i] - end_ns[trig] >= agg_ns, W if none, and at
+ *                 least trig + 1
+ *   summed [C] (or NULL) = logits[trig], then += logits[i] for i = trig + 1 .. stop - 1: each
+ *                 column by one thread, in row order, plain fp32 adds
+ *   out[2] pred = index of the first entry of that sum
+ * Without an alarm out = {-1, -1, -1} and summed is all 0.  workspace: lg_event_decide_workspace_bytes(W)
+ * bytes.  LG_EINVAL before any HIP call: W < 0, C < 1, ldx < C, noleak outside [0, C), NULL out, and
+ * for W > 0 NULL logits / end_ns / workspace or a workspace that is too small.  W == 0: no alarm. */
+int64_t lg_event_decide_workspace_bytes(int64_t W);
+int lg_event_decide(const float* logits, const int64_t* end_ns, int64_t W, int64_t C, int64_t ldx, int64_t agg_ns,
+                    int64_t noleak, int64_t* out, float* summed, void* workspace, int64_t workspace_bytes,
+                    lg_stream_t stream);
+
 /* Training-step tail: torch.nn.utils.clip_grad_norm_(params, max_norm) then
  * torch.optim.AdamW.step() (reference train_detector.py:313-317), ONE launch (ABI 23; two
  * before), two when the parameters need more 1024-element slices than the device has CUs.

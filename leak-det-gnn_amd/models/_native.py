@@ -149,6 +149,11 @@ SIGNATURES = {
                                         _p, _p]),
     "lg_cross_entropy_opt_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _p, _i64, _f32, _i32, _p,
                                         _i64, _p]),
+    # evaluator tails: window metrics and the event decision (added to ABI 26 without a bump: additions only)
+    "lg_window_metrics": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _i32, _p, _i32, _p, _i64, _p,
+                                 _p, _p]),
+    "lg_event_decide_workspace_bytes": (_i64, [_i64]),
+    "lg_event_decide": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _p]),
 }
 
 _lib = None

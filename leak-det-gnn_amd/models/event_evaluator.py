@@ -15,9 +15,12 @@ residual build and a B = 1 detector forward, pulling each logits row to the host
    `window_batch`), one host copy of the (W, P+1) logits.
 
 Trigger (`trigger_argmax`, `:327-331`) and aggregation (`aggregate_sum_logits`, `:334-342`)
-then run on the host copy with the reference's arithmetic: first window whose argmax is
-not the no-leak class; fp32 sum of that window's logits and the following ones whose end
-time is < agg_window after it, accumulated row by row in window order.
+use the reference's arithmetic: first window whose argmax is not the no-leak class; fp32
+sum of that window's logits and the following ones whose end time is < agg_window after
+it, accumulated row by row in window order.  On a CUDA device the logits stay there and
+leakgnn::event_decide (csrc/metrics.hip, two launches) returns [trigger, stop, predicted
+class], three integers per scenario; on the CPU `first_alarm` and `sum_logits_from` run on
+the logits themselves.
 
 Scenario selection (`:383-432`), tau from `leak_flow_m3h.csv` (`:204-223`), ATD via the
 pipe-distance oracle (`:96-170`), the per-event jsonl / summary.json outputs and the
@@ -40,6 +43,7 @@ import pandas as pd
 import torch
 import torch.nn as nn
 
+from . import ops
 from .datasets import SensorStandardizer, make_time_features
 from .utils import build_residual_sequence_from_segment
 from .window_evaluator import PipeDistanceOracle
@@ -188,12 +192,13 @@ def series_residual(predictor: nn.Module, pressure: torch.Tensor, tfeat: torch.T
 @torch.no_grad()
 def scenario_window_logits(predictor: nn.Module, detector: nn.Module, pressure: np.ndarray, tfeat: np.ndarray,
                            l_pred: int, l_det: int, stride: int, device: torch.device,
-                           window_batch: int = 256) -> Tuple[torch.Tensor, np.ndarray]:
+                           window_batch: int = 256, to_host: bool = True) -> Tuple[torch.Tensor, np.ndarray]:
     """Logits of every detection window of one scenario.
 
     Windows start at t0 = l_pred, l_pred + stride, ... <= T - l_det (`:476-492`); window
     t0 covers residual steps [t0, t0 + l_det) and time features tfeat[t0 : t0 + l_det].
-    Returns the (W, C) logits on the host and each window's last step index t0 + l_det - 1.
+    Returns the (W, C) logits, on the host or (to_host=False) where the detector left them, and
+    each window's last step index t0 + l_det - 1.
     """
     T = pressure.shape[0]
     t0 = np.arange(l_pred, T - l_det + 1, max(1, int(stride)), dtype=np.int64)
@@ -208,7 +213,8 @@ def scenario_window_logits(predictor: nn.Module, detector: nn.Module, pressure: 
     for c in range(0, t0.size, window_batch):
         rows = t0_dev[c:c + window_batch, None] + steps  # (w, l_det) absolute steps
         out.append(detector(res_all[rows - l_pred], tf[rows]).float())
-    return torch.cat(out).cpu(), t0 + l_det - 1
+    logits = torch.cat(out)
+    return (logits.cpu() if to_host else logits), t0 + l_det - 1
 
 
 # ------------------------------------------------------------------ scenario selection
@@ -289,6 +295,7 @@ def evaluate_dataset_event_level(
         out_path.mkdir(parents=True, exist_ok=True)
         (out_path / "per_event.jsonl").unlink(missing_ok=True)
 
+    on_gpu = torch.device(device).type == "cuda"
     picked = select_scenarios(read_manifest(manifest), pipe_ids_in_order, include_noleak, max_leak_scens,
                               max_noleak_scens, sample_seed)
     events: List[EventResult] = []
@@ -320,16 +327,22 @@ def evaluate_dataset_event_level(
         tau_iso = tau.isoformat() if tau is not None else None
 
         logits, last = scenario_window_logits(predictor, detector, pressure, tfeat, l_pred_steps, l_det_steps,
-                                              stride_steps, device, window_batch)
+                                              stride_steps, device, window_batch, to_host=not on_gpu)
         if logits.numel() and logits.shape[1] != num_classes:
             raise RuntimeError(f"Detector logits dim {logits.shape[1]} != expected num_classes {num_classes}")
-        trig = first_alarm(logits, noleak_class) if logits.numel() else None
+        ends = df.index[last]
+        if on_gpu and logits.numel():  # the logits stay on the device: three integers come back
+            end_ns = torch.from_numpy(np.ascontiguousarray(ends.asi8, dtype=np.int64)).to(logits.device)
+            decided, _ = ops.event_decide(logits, end_ns, int(agg_window.value), noleak_class)
+            trig, _, pred_idx = (int(v) for v in decided.tolist())
+            trig = None if trig < 0 else trig
+        else:
+            trig = first_alarm(logits, noleak_class) if logits.numel() else None
+            pred_idx = int(torch.argmax(sum_logits_from(logits, ends.asi8, trig, agg_window))) if trig is not None \
+                else -1
         if trig is None:
             ev = EventResult(str(sid), bool(leak_true), False, true_pid, None, tau_iso, None, None)
         else:
-            ends = df.index[last]
-            summed = sum_logits_from(logits, ends.asi8, trig, agg_window)
-            pred_idx = int(torch.argmax(summed))
             pred_leak = pred_idx != noleak_class
             pred_pid = pipe_ids_in_order[pred_idx] if pred_leak else None
             atd = float(dist.pipe_distance(pipe_to_idx[true_pid], pred_idx)) if (pred_leak and leak_true) else None

@@ -19,6 +19,8 @@ ordinary ops (fake / meta implementations give output shapes without running ker
   leakgnn::gnn_trunk           node init + L x [GCNConv, ReLU, Dropout] (detector.py:178-201)
   leakgnn::detector_heads      pipe gather + EdgeHead + mean pool + NoLeakHead
                                (detector.py:76-102, 206-218)
+  leakgnn::window_metrics      DetectorEvaluator.evaluate's per-batch tail (window_evaluator.py:227-483); no autograd
+  leakgnn::event_decide        the event evaluator's trigger + aggregation (event_evaluator.py:327-342); no autograd
 and one ``*_backward`` op per differentiable op (registered autograd formulas call them).
 
 Every op takes plain tensors (the graph CSR and its node tables are inputs, not Python
@@ -41,7 +43,8 @@ from torch import Tensor
 from . import _native as nat
 from ._native import check, load_library, ptr, stream_of
 from .ops import (EDGE_HEAD_SALT, GCN_BWD_NM_EXTRA_FLAGS, GCN_FWD_DENSE_EXTRA_FLAGS, GCN_FWD_NM_EXTRA_FLAGS,
-                  GRU_PRED_SALT, GRU_STACK_SALT, NM_MAX_BYTES, NOLEAK_HEAD_SALT, TCN_SALT, _check_d, _timed)
+                  GRU_PRED_SALT, GRU_STACK_SALT, NM_MAX_BYTES, NOLEAK_HEAD_SALT, TCN_SALT, WINDOW_COUNTERS,
+                  WINDOW_MAX_LIST, _check_d, _timed)
 
 NS = "leakgnn"
 
@@ -1789,6 +1792,88 @@ def _heads_bwd(ctx, dlogits, _dehid, _dpooled, _dhid):
 
 
 detector_heads.register_autograd(_heads_bwd, setup_context=_heads_setup)
+
+
+# ============================================================================ evaluator tails
+def _rows(op: str, logits: Tensor) -> Tuple[int, int, int]:
+    """(rows, C, row stride) of a (rows, C) fp32 CUDA matrix with unit column stride; no copy is made."""
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"{op}: logits must be a (rows, C) float32 matrix, got {tuple(logits.shape)} {logits.dtype}")
+    _req(logits)
+    n, C = logits.shape
+    if C > 1 and logits.stride(1) != 1:
+        raise ValueError(f"{op}: logits need unit column stride (strides {logits.stride()})")
+    ldx = logits.stride(0) if n > 1 else C
+    if ldx < C:
+        raise ValueError(f"{op}: logits rows overlap (row stride {ldx} < C = {C})")
+    return n, C, ldx
+
+
+def _vec(op: str, name: str, t: Optional[Tensor], dtype: torch.dtype, shape: Tuple[int, ...]) -> None:
+    if t is None:
+        return
+    if not t.is_cuda or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+        raise ValueError(f"{op}: {name} must be a contiguous {dtype} CUDA tensor of shape {shape}, got "
+                         f"{tuple(t.shape)} {t.dtype} on {t.device}")
+
+
+@torch.library.custom_op(f"{NS}::window_metrics", mutates_args=("counters",), device_types="cuda")
+def window_metrics(logits: Tensor, label: Tensor, nlc: int, topk: int, bucket: Optional[Tensor],
+                   dist: Optional[Tensor], inv_rank: Optional[Tensor], radii: List[float], acc_is: List[int],
+                   counters: Tensor) -> Tuple[Tensor, Tensor]:
+    """(rank_out, atd_out) of lg_window_metrics; `counters` (int64, ops.WINDOW_COUNTERS order) is
+    accumulated in place.  atd_out is empty without `dist`.  Allocates the two outputs, nothing
+    else, and never synchronises."""
+    op = "window_metrics"
+    lib = load_library()
+    B, C, ldx = _rows(op, logits)
+    _vec(op, "label", label, torch.int64, (B,))
+    _vec(op, "bucket", bucket, torch.int32, (B,))
+    _vec(op, "dist", dist, torch.float64, (nlc, nlc))
+    _vec(op, "inv_rank", inv_rank, torch.int32, (nlc, nlc))
+    _vec(op, "counters", counters, torch.int64, (len(WINDOW_COUNTERS),))
+    if len(radii) > WINDOW_MAX_LIST or len(acc_is) > WINDOW_MAX_LIST:
+        raise ValueError(f"{op}: at most {WINDOW_MAX_LIST} radii and accuracy_is per call, got {len(radii)} / {len(acc_is)}")
+    rank = torch.empty(B, dtype=torch.int32, device=logits.device)
+    atd = torch.empty(B if dist is not None else 0, dtype=torch.float64, device=logits.device)
+    if B == 0:
+        return rank, atd
+    rr = (ctypes.c_double * max(1, len(radii)))(*radii)
+    ii = (ctypes.c_int64 * max(1, len(acc_is)))(*acc_is)
+    check(lib.lg_window_metrics(ptr(logits), ptr(label), B, C, ldx, nlc, topk, ptr(bucket), ptr(dist), ptr(inv_rank),
+                                ctypes.cast(rr, ctypes.c_void_p), len(radii), ctypes.cast(ii, ctypes.c_void_p),
+                                len(acc_is), ptr(counters), counters.numel(), ptr(rank),
+                                ptr(atd) if dist is not None else None, stream_of(logits)), "lg_window_metrics")
+    return rank, atd
+
+
+@window_metrics.register_fake
+def _(logits, label, nlc, topk, bucket, dist, inv_rank, radii, acc_is, counters):
+    B = logits.shape[0]
+    return (logits.new_empty(B, dtype=torch.int32), logits.new_empty(B if dist is not None else 0, dtype=torch.float64))
+
+
+@torch.library.custom_op(f"{NS}::event_decide", mutates_args=(), device_types="cuda")
+def event_decide(logits: Tensor, end_ns: Tensor, agg_ns: int, noleak: int, want_sum: bool) -> Tuple[Tensor, Tensor]:
+    """(int64 [trig, stop, pred], summed fp32 (C,), empty unless want_sum) of lg_event_decide."""
+    op = "event_decide"
+    lib = load_library()
+    W, C, ldx = _rows(op, logits)
+    _vec(op, "end_ns", end_ns, torch.int64, (W,))
+    dev = logits.device
+    out = torch.empty(3, dtype=torch.int64, device=dev)
+    summed = torch.empty(C if want_sum else 0, dtype=torch.float32, device=dev)
+    nws = int(lib.lg_event_decide_workspace_bytes(W))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+    check(lib.lg_event_decide(ptr(logits) if W else None, ptr(end_ns) if W else None, W, C, ldx, agg_ns, noleak,
+                              ptr(out), ptr(summed) if want_sum else None, ptr(ws), nws, stream_of(logits)),
+          "lg_event_decide")
+    return out, summed
+
+
+@event_decide.register_fake
+def _(logits, end_ns, agg_ns, noleak, want_sum):
+    return (logits.new_empty(3, dtype=torch.int64), logits.new_empty(logits.shape[1] if want_sum else 0))
 
 
 # ============================================================================ module-facing helpers

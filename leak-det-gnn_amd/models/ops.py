@@ -487,6 +487,54 @@ def spmm(graph: GCNGraph, x: torch.Tensor, B: int = 1) -> torch.Tensor:
     return y
 
 
+# ----------------------------------------------------------------------------- evaluator tails
+# Slot layout of lg_window_metrics' counters (include/leakgnn.h; csrc/metrics.hip holds the same
+# order as an enum and the library refuses a tensor of another length).  The names are those
+# DetectorEvaluator.evaluate accumulates under; success[r] / acc_i[i] are per position in the radii /
+# accuracy_is lists of the call, and evaluate's pre_total / noleak_only_total are two of the bucket
+# totals (WINDOW_COUNTER_ALIASES).
+WINDOW_BUCKETS = ("early", "late", "pre", "noleak")  # bucket codes 0..3 (window_evaluator._BUCKETS); -1: none
+WINDOW_MAX_LIST = 8                                  # LG_WM_MAX_LIST: radii and accuracy_is entries per call
+WINDOW_COUNTERS = (
+    ("total", "correct1", "correctk", "nl_total", "nl_correct", "leak_total", "leak_correct1", "leak_correctk",
+     "tp", "fp", "fn", "tn")
+    + tuple(f"{k}_{b}" for b in WINDOW_BUCKETS for k in ("b_total", "b_correct1", "b_correctk", "b_pred_nl"))
+    + ("pre_false_alarm", "noleak_false_alarm")
+    + tuple(f"success[{r}]" for r in range(WINDOW_MAX_LIST))
+    + tuple(f"acc_i[{i}]" for i in range(WINDOW_MAX_LIST))
+    + ("bad_label",))
+WINDOW_COUNTER_ALIASES = {"pre_total": "b_total_pre", "noleak_only_total": "b_total_noleak"}
+
+
+def window_counters(device: torch.device) -> torch.Tensor:
+    """A zeroed counter tensor for window_metrics to accumulate into."""
+    return torch.zeros(len(WINDOW_COUNTERS), dtype=torch.int64, device=device)
+
+
+def window_metrics(logits: torch.Tensor, label: torch.Tensor, nlc: int, counters: torch.Tensor, *, topk: int = 5,
+                   bucket: Optional[torch.Tensor] = None, dist: Optional[torch.Tensor] = None,
+                   inv_rank: Optional[torch.Tensor] = None, radii: Sequence[float] = (),
+                   acc_is: Sequence[int] = ()) -> tuple:
+    """One evaluated batch (lg_window_metrics, one launch, no synchronisation): adds the batch's
+    counts to `counters` (int64, WINDOW_COUNTERS order) and returns (rank int32 (B,), atd float64
+    (B,) or None without `dist`): rank 0 / atd NaN mark the no-leak rows.  logits: fp32 (B, C) with
+    unit column stride (a row-sliced view is fine); label int64; bucket int32 codes; dist float64
+    (nlc, nlc); inv_rank int32 (nlc, nlc)."""
+    from . import library  # noqa: F401  (registers torch.ops.leakgnn.*)
+    rank, atd = torch.ops.leakgnn.window_metrics(logits, label, int(nlc), int(topk), bucket, dist, inv_rank,
+                                                 [float(r) for r in radii], [int(i) for i in acc_is], counters)
+    return rank, (atd if dist is not None else None)
+
+
+def event_decide(logits: torch.Tensor, end_ns: torch.Tensor, agg_ns: int, noleak: int, want_sum: bool = False) -> tuple:
+    """Trigger and aggregation over one scenario's (W, C) window logits (lg_event_decide, two
+    launches, no synchronisation): (int64 [trig, stop, pred] on the device, the fp32 summed row or
+    None).  trig = -1: no window's first entry differs from `noleak`."""
+    from . import library  # noqa: F401
+    out, summed = torch.ops.leakgnn.event_decide(logits, end_ns, int(agg_ns), int(noleak), bool(want_sum))
+    return out, (summed if want_sum else None)
+
+
 def wall_ms(fn, iters: int = 10) -> float:
     torch.cuda.synchronize()
     t0 = time.perf_counter()

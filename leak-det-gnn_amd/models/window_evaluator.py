@@ -11,6 +11,13 @@ each); here every count is a device reduction over the batch and one small tenso
 comes back per batch.  Pipe distances are a precomputed P x P table (the reference's own
 midpoint formula on Dijkstra node distances, float64, plus its float32 rank table from
 np.argsort), gathered per sample on the device.
+
+Fused route (fp32 CUDA logits, `fused=None` or `True`): the per-batch tail below the detector
+call is ONE launch of leakgnn::window_metrics (csrc/metrics.hip) into one int64 counter tensor per
+evaluate() call; the per-row ranks and distances stay on the device until the loader is exhausted,
+so the loop reads nothing back.  Ties between logits, which torch's argmax / topk / argsort leave
+open on a GPU, follow the order stated in include/leakgnn.h.  `fused=False` is the torch route
+below, the only one for CPU tensors.
 """
 from __future__ import annotations
 
@@ -24,6 +31,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import ops
 from .utils import build_residual_sequence_from_segment, now, parse_epanet_inp
 
 
@@ -170,7 +178,7 @@ class DetectorEvaluator:
                  l_det: int, topk: int = 5, metric_groups: Sequence[str] = ("basic", "binary", "bucket"),
                  inp_path: Optional[str | Path] = None, pipe_ids_in_order: Optional[Sequence[str]] = None,
                  success_radii_m: Sequence[float] = (50.0, 100.0, 300.0),
-                 accuracy_is: Sequence[int] = (1, 5, 10, 20)) -> None:
+                 accuracy_is: Sequence[int] = (1, 5, 10, 20), fused: Optional[bool] = None) -> None:
         self.predictor = predictor
         self.detector = detector
         self.device = torch.device(device)
@@ -181,6 +189,8 @@ class DetectorEvaluator:
         self.success_radii_m = [float(x) for x in success_radii_m]
         self.accuracy_is = [int(i) for i in accuracy_is]
         self.residual_builder = build_residual_sequence_from_segment
+        self.fused = None if fused is None else bool(fused)
+        self._inv_rank_i32: Optional[torch.Tensor] = None  # the fused route's table, uploaded once
         print(f"{now()} [metric_evaluator] building evaluator for metrics: {self.metric_groups}.")
         self.oracle: Optional[PipeDistanceOracle] = None
         self._dist = self._inv_rank = None
@@ -196,6 +206,37 @@ class DetectorEvaluator:
                 inv.scatter_(1, rank, torch.arange(rank.shape[1]).expand_as(rank))
                 self._inv_rank = inv.to(self.device)  # inv[p, y] = position of y in pipe_rank[p]
 
+    def _fused_for(self, logits: torch.Tensor) -> bool:
+        """Whether this evaluate() call runs its tail on leakgnn::window_metrics."""
+        able = (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2
+                and len(self.success_radii_m) <= ops.WINDOW_MAX_LIST and len(self.accuracy_is) <= ops.WINDOW_MAX_LIST)
+        if self.fused and not able:
+            raise ValueError(f"fused=True needs fp32 CUDA logits and at most {ops.WINDOW_MAX_LIST} success radii and "
+                             f"accuracy_is (logits: {logits.dtype} on {logits.device}); fused=False is the torch route")
+        return able if self.fused is None else self.fused
+
+    def _fused_inv_rank(self) -> Optional[torch.Tensor]:
+        if self._inv_rank is not None and self._inv_rank_i32 is None:
+            self._inv_rank_i32 = self._inv_rank.to(torch.int32).contiguous()
+        return self._inv_rank_i32
+
+    def _fused_counts(self, counters: torch.Tensor) -> Dict[str, float]:
+        """The counter tensor under the names the torch route accumulates."""
+        vals = counters.cpu().tolist()
+        slot = {name: float(v) for name, v in zip(ops.WINDOW_COUNTERS, vals)}
+        if slot["bad_label"]:
+            raise ValueError(f"{int(slot['bad_label'])} evaluated windows have a label outside [0, num_classes)")
+        c = {name: v for name, v in slot.items() if "[" not in name and name != "bad_label"}
+        for alias, name in ops.WINDOW_COUNTER_ALIASES.items():
+            c[alias] = slot[name]
+        if self._dist is not None:  # a radius listed twice is added twice, as the torch route does
+            for j, r in enumerate(self.success_radii_m):
+                c[f"success_{r}"] = c.get(f"success_{r}", 0.0) + slot[f"success[{j}]"]
+            if self._inv_rank is not None:
+                for j, ii in enumerate(self.accuracy_is):
+                    c[f"acc_i_{ii}"] = c.get(f"acc_i_{ii}", 0.0) + slot[f"acc_i[{j}]"]
+        return c
+
     @torch.no_grad()
     def evaluate(self, loader: Iterable[Dict[str, Any]]) -> Dict[str, float]:
         self.predictor.eval()
@@ -209,25 +250,44 @@ class DetectorEvaluator:
 
         ar_ranks: List[torch.Tensor] = []
         atd_vals: List[torch.Tensor] = []
+        fused: Optional[bool] = None           # decided on the first batch's logits, for the whole call
+        counters: Optional[torch.Tensor] = None  # fused route: every count of this call, on the device
         for batch in loader:
             noisy_seg = batch["noisy_seg"].to(dev)
             time_seg = batch["time_seg"].to(dev)
             label = torch.as_tensor(batch["label"], device=dev, dtype=torch.long)
             n = label.numel()
             bucket_list = batch.get("bucket", None) or ["unknown"] * n
-            bcode = torch.tensor([_BUCKETS.index(str(b)) if str(b) in _BUCKETS else -1 for b in bucket_list],
-                                 device=dev)
+            bcode_host = [_BUCKETS.index(str(b)) if str(b) in _BUCKETS else -1 for b in bucket_list]
+            residual = self.residual_builder(self.predictor, noisy_seg, time_seg, l_pred=self.l_pred,
+                                             l_det=self.l_det, device=dev)
+            logits = self.detector(residual, time_seg[:, self.l_pred:, :])
+            if fused is None:
+                fused = self._fused_for(logits)
             num_classes = batch.get("num_classes", None)
             if isinstance(num_classes, (list, tuple)):
                 num_classes = int(num_classes[0])
             elif torch.is_tensor(num_classes):
-                num_classes = int(num_classes[0].item())
-            residual = self.residual_builder(self.predictor, noisy_seg, time_seg, l_pred=self.l_pred,
-                                             l_det=self.l_det, device=dev)
-            logits = self.detector(residual, time_seg[:, self.l_pred:, :])
+                # a device tensor (DeviceBatchLoader) would cost the fused route a read-back per batch:
+                # there the class count is the logits' width, which is what every loader here writes
+                num_classes = None if (fused and num_classes.is_cuda) else int(num_classes[0].item())
             if num_classes is None:
                 num_classes = int(logits.size(-1))
             nlc = num_classes - 1
+            if fused:
+                if counters is None:
+                    counters = ops.window_counters(logits.device)
+                codes = torch.tensor(bcode_host, dtype=torch.int32, device=dev) if "bucket" in self.metric_groups \
+                    else None
+                rank, atd = ops.window_metrics(logits, label, nlc, counters, topk=self.topk, bucket=codes,
+                                               dist=self._dist, inv_rank=self._fused_inv_rank(),
+                                               radii=self.success_radii_m if self._dist is not None else (),
+                                               acc_is=self.accuracy_is if self._inv_rank is not None else ())
+                ar_ranks.append(rank)
+                if atd is not None:
+                    atd_vals.append(atd)
+                continue
+            bcode = torch.tensor(bcode_host, device=dev)
             pred1 = logits.argmax(dim=-1)
             k = min(self.topk, logits.size(-1))
             hitk = (logits.topk(k=k, dim=-1).indices == label.unsqueeze(1)).any(dim=1)
@@ -282,6 +342,13 @@ class DetectorEvaluator:
                         add(f"acc_i_{ii}", ((~missed) & (pos < ii) & (ii > 0)).sum())
 
         c = {name: float(v.item()) for name, v in acc.items()}
+        if counters is not None:  # fused route: the first read-back of the call
+            c = self._fused_counts(counters)
+            ranks = torch.cat(ar_ranks)
+            ar_ranks = [ranks[ranks > 0].to(torch.int64)]     # the leak rows, in row order
+            if atd_vals:
+                d = torch.cat(atd_vals)
+                atd_vals = [d[~torch.isnan(d)]]
         g = lambda name: c.get(name, 0.0)  # noqa: E731
 
         def safe_div(a: float, b: float) -> float:
