@@ -1033,6 +1033,67 @@ int lg_head_mse_bwd(const float* h, const float* weight, const float* target, co
                     const float* grad_loss, int64_t B, int64_t H, int64_t S, float* dh, float* dweight,
                     float* dbias, void* workspace, int64_t ws_bytes, lg_stream_t stream);
 
+/* ---- Device sampler: the datasets' per-sample draws and the window gather --------------
+ * (models/datasets.py AbruptLeakDetectorDataset.draw / NormalPredictorDataset.draw, reference
+ * datasets.py:236-243, 483-517; added to ABI 26 without a bump: additions only.)
+ * Sample idx of a dataset is a pure function of numpy's default_rng(seed + idx).  The draw entry
+ * points replay that stream (csrc/np_rng.h: SeedSequence, PCG64, random(), integers(), scalar
+ * choice()) for the n samples idx = i0 .. i0 + n - 1, one thread per sample, and write one
+ * int32[LG_DRAW_RECORD] record per sample:
+ *   [bank scene index, t, label, pipe_index, bucket code, attempts, 0, 0]
+ * (bucket codes: 0 early, 1 late, 2 pre, 3 noleak; -1 for the predictor).  seed + idx is taken
+ * modulo 2^64: callers keep it below 2^64, where numpy's entropy has at most two 32-bit words.
+ *   lg_draw_detector   tables over the n_scenes scenes of the HBM bank: leak_list [n_leak] and
+ *       noleak_list [n_noleak] hold the bank index of each entry of the dataset's two scene lists
+ *       (choice draws a POSITION in the list); times [n_scenes][4][2] is (start, count) of the
+ *       scene's time list per bucket (every list is a contiguous arange; count 0 = empty, the
+ *       attempt is repeated, up to 10); pipe [n_scenes] the scene's pipe index (-1: no-leak scene).
+ *       cum_host: the four cumulative bucket probabilities (fp64, compared as the dataset compares
+ *       them).  label = pipe for early / late, no_leak_class for pre / noleak.
+ *   lg_draw_predictor  scene = scene_list[choice(n_list)], t = integers(l_in - 1, scene_len[scene] - h).
+ * A sample that cannot be decided (ten empty time lists; a list entry outside [0, n_scenes); a
+ * scene shorter than l_in + h) gets the record [-1, -1, -1, -1, -1, attempts, 0, 0] and adds 1 to
+ * err[0]; nothing else happens on the device.  err is TWO device uint32 words, zeroed by the caller.
+ * n <= LG_DRAW_MAX_SAMPLES per call; a null pointer or a size out of range is LG_EINVAL before any
+ * HIP call.  Populations of 2^32 entries or more are refused with LG_EINVAL, never truncated.
+ *   lg_gather_windows  one workgroup per sample s of records[0 .. n): up to three segments k (src_k
+ *       NULL = unused), dst_k[s] = src_k[scene][t + off_k .. t + off_k + len_k) as len_k * C_k
+ *       floats (src_k is a bank tensor [n_scenes][T_max][C_k], dst_k [n][len_k][C_k]; dword
+ *       copies, rows are only 4-byte aligned), plus label / pipe_index (int64) and bucket_code
+ *       (int32) of the sample (each may be NULL).  A record with label < 0 yields zeros and -1s and
+ *       no address is formed from it; a record whose windows do not lie inside the bank is treated
+ *       the same and adds 1 to err[1].
+ *   *_host             the same draw code on the CPU over host tables (tests, no device needed).
+ *   lg_np_stream_host  replays a script of n calls on default_rng(seed): ops_host[k] LG_NP_RANDOM ->
+ *       out_f_host[k] = random(); LG_NP_BOUNDED -> out_i_host[k] = integers(low_host[k],
+ *       low_host[k] + count_host[k]), 1 <= count <= 2^32 (else LG_EINVAL, before any draw). */
+#define LG_DRAW_RECORD 8
+#define LG_DRAW_MAX_SAMPLES (1 << 20)
+#define LG_NP_RANDOM 0
+#define LG_NP_BOUNDED 1
+int lg_draw_detector(uint64_t seed, int64_t i0, int64_t n, const int32_t* leak_list, int64_t n_leak,
+                     const int32_t* noleak_list, int64_t n_noleak, const int32_t* times, const int32_t* pipe,
+                     int64_t n_scenes, const double* cum_host, int64_t no_leak_class, int32_t* records,
+                     uint32_t* err, lg_stream_t stream);
+int lg_draw_detector_host(uint64_t seed, int64_t i0, int64_t n, const int32_t* leak_list_host, int64_t n_leak,
+                          const int32_t* noleak_list_host, int64_t n_noleak, const int32_t* times_host,
+                          const int32_t* pipe_host, int64_t n_scenes, const double* cum_host,
+                          int64_t no_leak_class, int32_t* records_host, uint32_t* err_host);
+int lg_draw_predictor(uint64_t seed, int64_t i0, int64_t n, const int32_t* scene_list, int64_t n_list,
+                      const int32_t* scene_len, int64_t n_scenes, int64_t l_in, int64_t h, int32_t* records,
+                      uint32_t* err, lg_stream_t stream);
+int lg_draw_predictor_host(uint64_t seed, int64_t i0, int64_t n, const int32_t* scene_list_host, int64_t n_list,
+                           const int32_t* scene_len_host, int64_t n_scenes, int64_t l_in, int64_t h,
+                           int32_t* records_host, uint32_t* err_host);
+int lg_np_stream_host(uint64_t seed, const int32_t* ops_host, const int64_t* low_host, const uint64_t* count_host,
+                      int64_t n, double* out_f_host, int64_t* out_i_host);
+int lg_gather_windows(const int32_t* records, int64_t n, int64_t n_scenes, int64_t T_max,
+                      const float* src0, int64_t C0, int64_t off0, int64_t len0, float* dst0,
+                      const float* src1, int64_t C1, int64_t off1, int64_t len1, float* dst1,
+                      const float* src2, int64_t C2, int64_t off2, int64_t len2, float* dst2,
+                      int64_t* label, int64_t* pipe_index, int32_t* bucket_code, uint32_t* err,
+                      lg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

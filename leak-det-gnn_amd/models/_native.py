@@ -154,6 +154,15 @@ SIGNATURES = {
                                  _p, _p]),
     "lg_event_decide_workspace_bytes": (_i64, [_i64]),
     "lg_event_decide": (_i32, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p, _p, _p, _i64, _p]),
+    # device sampler: numpy-exact draws and the window gather (added to ABI 26 without a bump: additions only)
+    "lg_draw_detector": (_i32, [_u64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p, _p]),
+    "lg_draw_detector_host": (_i32, [_u64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p]),
+    "lg_draw_predictor": (_i32, [_u64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "lg_draw_predictor_host": (_i32, [_u64, _i64, _i64, _p, _i64, _p, _i64, _i64, _i64, _p, _p]),
+    "lg_np_stream_host": (_i32, [_u64, _p, _p, _p, _i64, _p, _p]),
+    "lg_gather_windows": (_i32, [_p, _i64, _i64, _i64,
+                                 _p, _i64, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _i64, _i64, _p,
+                                 _p, _p, _p, _p, _p]),
 }
 
 _lib = None

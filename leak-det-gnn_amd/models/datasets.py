@@ -17,6 +17,9 @@ forms a whole batch of windows with ONE device gather — no per-sample CSV/LRU 
 no host-to-device copy of windows per step.  It yields the same batch dicts a
 ``torch.utils.data.DataLoader(ds, batch_size, shuffle=False)`` would, with the tensors
 already on the device.
+``draw="device"`` moves the per-sample decisions to the device as well: a HIP kernel
+replays numpy's stream of ``default_rng(seed + idx)`` (models/sampler.py, csrc/sampler.hip),
+a second one gathers the windows, and the batches are bit-identical to the host mode's.
 """
 from __future__ import annotations
 
@@ -439,7 +442,11 @@ class DeviceBatchLoader:
     order, windows gathered on ``device`` from HBM-resident scenes.  Equivalent to
     DataLoader(ds, batch_size, shuffle=False) + .to(device) of the tensor fields."""
 
-    def __init__(self, ds, batch_size: int, device: torch.device, shard: Tuple[int, int] = (0, 1)) -> None:
+    def __init__(self, ds, batch_size: int, device: torch.device, shard: Tuple[int, int] = (0, 1),
+                 draw: str = "host") -> None:
+        if draw not in ("host", "device"):
+            raise ValueError(f"draw must be 'host' or 'device', got {draw!r}")
+        self.draw = draw
         self.ds = ds
         self.batch_size = int(batch_size)
         self.device = torch.device(device)
@@ -451,9 +458,32 @@ class DeviceBatchLoader:
             self.bank = _DeviceBank(ds.store, list(ds.scene_ids), self.device, with_gt=True)
         else:
             raise TypeError(f"unsupported dataset {type(ds).__name__}")
+        self._sampler = None
+        if draw == "device":  # tables from the dataset's lists as they are NOW (the trainers set them first)
+            from .sampler import DeviceSampler
+            kind = "detector" if isinstance(ds, AbruptLeakDetectorDataset) else "predictor"
+            self._sampler = DeviceSampler(ds, self.bank, kind)
 
     def __len__(self) -> int:
         return (len(self.ds) + self.batch_size - 1) // self.batch_size
+
+    def materialize(self, batch: Dict[str, Any]) -> Dict[str, Any]:
+        """A draw="device" batch read back into exactly the dict draw="host" yields (the id,
+        bucket, timestamp and pipe-id strings added, the device-only keys removed)."""
+        if self._sampler is None:
+            return batch
+        return self._sampler.materialize(batch)
+
+    def _iter_device(self) -> Iterator[Dict[str, Any]]:
+        """draw="device": every sample of [0, len(ds)) decided by the draw kernel up front, then one
+        gather launch per batch; nothing is read back until the error words at the end."""
+        sm, n = self._sampler, len(self.ds)
+        err = sm.new_error_words()
+        rec = sm.draw_range(0, n, err)
+        for b0 in range(0, n, self.batch_size):
+            r = shard_slice(range(b0, min(b0 + self.batch_size, n)), self.rank, self.world)
+            yield sm.gather(rec, r.start, r.stop, err)
+        sm.check_errors(err)
 
     def _detector_batch(self, idxs: range) -> Dict[str, Any]:
         ds, bank = self.ds, self.bank
@@ -489,6 +519,9 @@ class DeviceBatchLoader:
         }
 
     def __iter__(self) -> Iterator[Dict[str, Any]]:
+        if self._sampler is not None:
+            yield from self._iter_device()
+            return
         make = self._detector_batch if isinstance(self.ds, AbruptLeakDetectorDataset) else self._predictor_batch
         for b0 in range(0, len(self.ds), self.batch_size):
             yield make(shard_slice(range(b0, min(b0 + self.batch_size, len(self.ds))), self.rank, self.world))

@@ -197,7 +197,9 @@ def main(argv=None, *, parse_only: bool = False):
     ap.add_argument("--device", type=str, default="auto")
     ap.add_argument("--num_workers", type=int, default=0)
     ap.add_argument("--log_every", type=int, default=50)
-    ap.add_argument("--loader", type=str, default="device", choices=["device", "torch"])
+    ap.add_argument("--loader", type=str, default="device", choices=["device", "device_draw", "torch"],
+                    help="device: scenes in HBM, samples drawn on the host; device_draw: drawn by a HIP kernel as "
+                         "well (same batches, no host work per sample); torch: the reference's DataLoader")
     ap.add_argument("--dtype", type=str, default="fp32", choices=["fp32", "bf16"],
                     help="node-MLP tier: fp32 (fp32 parity) or bf16 (GCN transforms and EdgeHead MLP as one bf16 "
                          "MFMA product, BASELINE configs[2])")

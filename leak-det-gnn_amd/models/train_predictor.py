@@ -130,6 +130,10 @@ def make_loader(ds, batch_size: int, device: torch.device, kind: str, num_worker
                 shard: Tuple[int, int] = (0, 1)):
     """Batches of `batch_size` samples in index order; with shard = (rank, world) each rank
     gets its contiguous slice of every global batch (data parallelism)."""
+    if kind == "device_draw":  # the per-sample draws on the device as well (datasets.DeviceBatchLoader, draw="device")
+        if device.type != "cuda":
+            raise ValueError("--loader device_draw needs the GPU path (--device cuda)")
+        return DeviceBatchLoader(ds, batch_size, device, shard=shard, draw="device")
     if kind == "device" and device.type == "cuda":
         return DeviceBatchLoader(ds, batch_size, device, shard=shard)
     if shard[1] > 1:
@@ -174,7 +178,9 @@ def main(argv=None) -> None:
     ap.add_argument("--device", type=str, default="auto", help="auto|cuda|cpu|cuda:0 ...")
     ap.add_argument("--num_workers", type=int, default=0)
     ap.add_argument("--log_every", type=int, default=50)
-    ap.add_argument("--loader", type=str, default="device", choices=["device", "torch"])
+    ap.add_argument("--loader", type=str, default="device", choices=["device", "device_draw", "torch"],
+                    help="device: scenes in HBM, samples drawn on the host; device_draw: drawn by a HIP kernel as "
+                         "well (same batches, no host work per sample); torch: the reference's DataLoader")
     ap.add_argument("--capture", type=str, default="auto", choices=["auto", "on", "off"],
                     help="replay each full-size training batch's step as one captured HIP graph "
                          "(models/graph_step.py; auto = on for the GPU path where it measured faster); "

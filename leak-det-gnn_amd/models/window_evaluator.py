@@ -257,8 +257,13 @@ class DetectorEvaluator:
             time_seg = batch["time_seg"].to(dev)
             label = torch.as_tensor(batch["label"], device=dev, dtype=torch.long)
             n = label.numel()
-            bucket_list = batch.get("bucket", None) or ["unknown"] * n
-            bcode_host = [_BUCKETS.index(str(b)) if str(b) in _BUCKETS else -1 for b in bucket_list]
+            bcode_dev = batch.get("bucket_code", None)  # DeviceBatchLoader(draw="device"): int32 codes on the device
+            if torch.is_tensor(bcode_dev):
+                bcode_dev, bcode_host = bcode_dev.to(dev), None  # no host list is built
+            else:
+                bucket_list = batch.get("bucket", None) or ["unknown"] * n
+                bcode_host = [_BUCKETS.index(str(b)) if str(b) in _BUCKETS else -1 for b in bucket_list]
+                bcode_dev = None
             residual = self.residual_builder(self.predictor, noisy_seg, time_seg, l_pred=self.l_pred,
                                              l_det=self.l_det, device=dev)
             logits = self.detector(residual, time_seg[:, self.l_pred:, :])
@@ -277,8 +282,10 @@ class DetectorEvaluator:
             if fused:
                 if counters is None:
                     counters = ops.window_counters(logits.device)
-                codes = torch.tensor(bcode_host, dtype=torch.int32, device=dev) if "bucket" in self.metric_groups \
-                    else None
+                codes = None
+                if "bucket" in self.metric_groups:
+                    codes = bcode_dev.to(torch.int32).contiguous() if bcode_dev is not None else \
+                        torch.tensor(bcode_host, dtype=torch.int32, device=dev)
                 rank, atd = ops.window_metrics(logits, label, nlc, counters, topk=self.topk, bucket=codes,
                                                dist=self._dist, inv_rank=self._fused_inv_rank(),
                                                radii=self.success_radii_m if self._dist is not None else (),
@@ -287,7 +294,7 @@ class DetectorEvaluator:
                 if atd is not None:
                     atd_vals.append(atd)
                 continue
-            bcode = torch.tensor(bcode_host, device=dev)
+            bcode = bcode_dev if bcode_dev is not None else torch.tensor(bcode_host, device=dev)
             pred1 = logits.argmax(dim=-1)
             k = min(self.topk, logits.size(-1))
             hitk = (logits.topk(k=k, dim=-1).indices == label.unsqueeze(1)).any(dim=1)
