@@ -593,6 +593,33 @@ int lg_gcn_bwd_nm_bits(const int32_t* nodetab_t, const int32_t* pairs_t, const f
                        int flags, float scale_in, float scale_out, void* workspace, int64_t ws_bytes, lg_stream_t stream,
                        const uint16_t* ymask);
 
+/* Residual (identity-skip) layer, x_out = x + f(x) with f = dropout(relu(Ahat x W^T + b))
+ * (added to ABI 26 without a bump: additions only).  A deep trunk is trained with identity
+ * skips; the plain backward recovers a layer's ReLU/dropout mask as [y > 0], which is wrong
+ * once y = x + f, so both calls carry the branch's own mask as bits.
+ * lg_gcn_fwd_nm_skip: lg_gcn_fwd_nm_bits' arguments; ymask is required (LG_EINVAL).
+ *   y = x_own + f, where f is exactly lg_gcn_fwd_nm_bits' y for the same arguments and ymask
+ *   holds [f > 0] (NOT [y > 0]), bit for bit that call's ymask.  The sum is one fp32 add per
+ *   element, the last operation before the store.  x and y must not alias.  Runs on the
+ *   producer / consumer kernel of the fp32 tier only (the f16x2 transform, or LG_F_BF16X3):
+ *   LG_F_BF16, LG_F_NM3 and LG_F_F32_MFMA return LG_EUNSUPPORTED.
+ * lg_gcn_bwd_nm_skip: lg_gcn_bwd_nm_bits' arguments; LG_F_MASK_IN and ymask (the forward's
+ *   [f > 0] bits) are required (LG_EINVAL), LG_F_BF16 returns LG_EUNSUPPORTED.  With
+ *   dz = dy * scale_in * mask:  t = Ahat^T dz, dW and db exactly as lg_gcn_bwd_nm_bits';
+ *   dx = t W + dy_own (one fp32 add after the product); then LG_F_MASK_OUT as there:
+ *   dx_out = (t W + dy) * scale_out * [x > 0].  LG_F_DX_SENSOR_ROWS and dnode_bias keep their
+ *   meaning on the summed dx (dnode_bias is summed in another, still fixed, order than
+ *   lg_gcn_bwd_nm_bits').  dy and dx_out must not alias. */
+int lg_gcn_fwd_nm_skip(const int32_t* nodetab, const int32_t* pairs, const float* x, const float* W,
+                       const float* bias, float* y, int64_t B, int64_t N, int64_t D, int64_t nnz_cap,
+                       int flags, float dropout_p, uint64_t seed, uint32_t salt, lg_stream_t stream,
+                       uint16_t* ymask);
+int lg_gcn_bwd_nm_skip(const int32_t* nodetab_t, const int32_t* pairs_t, const float* dy, const float* y,
+                       const float* x, const float* W, float* dx_out, float* dW, float* db,
+                       const int32_t* node_slot, float* dnode_bias, int64_t B, int64_t N, int64_t D,
+                       int flags, float scale_in, float scale_out, void* workspace, int64_t ws_bytes, lg_stream_t stream,
+                       const uint16_t* ymask);
+
 /* Compressed layer-0 input (ABI 21).  The node init's non-sensor rows are dropout(relu(b)):
  * 632 of L-TOWN-A's 661 rows carry no information beyond their keep bits, yet materialising
  * x0 costs a 43 MB write and layer 0's forward and backward read it back (86 MB).

@@ -631,7 +631,12 @@ struct PcX0 {
     uint32_t S;
 };
 
-template <int D, bool DROP, bool RELU, bool BF, bool F16, int kPcProd, int NC, bool X0 = false>
+// SKIP (lg_gcn_fwd_nm_skip, the residual trunk): y = x_own + f, f the layer as above.  The
+// consumer loads the tile's own 16 x D block of x as whole rows (its self-loop neighbour, which
+// the producers gathered a moment ago) with the compiler's loads -- outside the producers'
+// prefetch registers and vmcnt counts --, takes the mask bits from f and adds x as the last
+// fp32 operation before the store.
+template <int D, bool DROP, bool RELU, bool BF, bool F16, int kPcProd, int NC, bool X0 = false, bool SKIP = false>
 __global__ void __launch_bounds__(64 * kPcProd * (1 + NC), kPcProd * (1 + NC) / 4)
 k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, const float* __restrict__ x,
              const float* __restrict__ W, const float* __restrict__ bias, float* __restrict__ y, uint32_t N,
@@ -646,6 +651,7 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
     constexpr int R = kPcRing;
     constexpr int NT = 64 * kPcProd * (1 + NC);
     static_assert(!(BF && F16), "one transform");
+    static_assert(!SKIP || (!X0 && !BF), "the skip lives on the dense fp32-tier layers");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* lds = reinterpret_cast<float*>(smem);
     float* wst = lds + LY::WOFF;
@@ -1088,7 +1094,8 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
 
     // ---------------- consumer: transform + epilogue
     const __amdgpu_buffer_rsrc_t yrs = nm_rsrc(y, bytes);
-    const __amdgpu_buffer_rsrc_t srs = nm_rsrc(x, X0 ? static_cast<uint64_t>(x0.S) * B * (4u * D) : 0);  // X0: xs0
+    // X0: xs0; SKIP: x, for the tile's own block
+    const __amdgpu_buffer_rsrc_t srs = nm_rsrc(x, X0 ? static_cast<uint64_t>(x0.S) * B * (4u * D) : (SKIP ? bytes : 0));
     const __amdgpu_buffer_rsrc_t mrs = nm_mask_rsrc(ymask, N, ngroups);
     uint32_t loff[G::K];
 #pragma unroll
@@ -1133,6 +1140,14 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
         const uint32_t* m = meta + kPcMeta * (prod * R + sl);
         const uint32_t n = __builtin_amdgcn_readfirstlane(m[0]), b0 = __builtin_amdgcn_readfirstlane(m[1]),
                        nb = __builtin_amdgcn_readfirstlane(m[2]);
+        f32x4 xo[SKIP ? G::K : 1];  // SKIP: the tile's own rows of x, in flight under the transform
+        if constexpr (SKIP) {
+#pragma unroll
+            for (int k = 0; k < G::K; ++k) {
+                const uint32_t lk = (G::RPI * k + rl) < static_cast<int>(nb) ? loff[k] : kNm3RowOob;
+                xo[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srs, lk, (n * B + b0) * (4u * D), 0));
+            }
+        }
         f32x4 bq[KS][2];
 #pragma unroll
         for (int s2 = 0; s2 < KS; ++s2) {
@@ -1248,10 +1263,11 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
         for (int k = 0; k < G::K; ++k) {
             const uint32_t lk = (G::RPI * k + rl) < static_cast<int>(nb) ? loff[k] : kNm3RowOob;
             vk[k] = ld4(slot + LY::tix(G::RPI * k + rl, fg));
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) uint32_t, vk[k]),
-                                                   yrs, lk, ob, kLgActAux);
+            if constexpr (!SKIP)
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) uint32_t, vk[k]),
+                                                       yrs, lk, ob, kLgActAux);
         }
-        if (ymask) {
+        if (ymask) {  // SKIP: the bits of f, before x is added
             uint32_t bits = 0;
 #pragma unroll
             for (int k = G::K - 1; k >= 0; --k)
@@ -1263,6 +1279,15 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
                 }
             __builtin_amdgcn_raw_buffer_store_b16(static_cast<uint16_t>(bits), mrs, nm_mask_off(n, b0 >> 4, ngroups, lane),
                                                   0, kLgActAux);
+        }
+        if constexpr (SKIP) {  // y = x_own + f: one fp32 add per element, then the store
+#pragma unroll
+            for (int k = 0; k < G::K; ++k) {
+                const uint32_t lk = (G::RPI * k + rl) < static_cast<int>(nb) ? loff[k] : kNm3RowOob;
+                vk[k] = xo[k] + vk[k];
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) uint32_t, vk[k]),
+                                                       yrs, lk, ob, kLgActAux);
+            }
         }
         lg_store_guard(vk);
         pc_store_rel(&done[prod * NC + cons], static_cast<uint32_t>(u + 1));  // the slot's reads are done (release)
@@ -1335,7 +1360,12 @@ struct NbX0 {
 // wave's own tile: a wave max each, 2^st, 2^sx).  dx^T is unscaled by 2^-(sW + st); dW
 // accumulates in units of 2^T, T = st + sx of the latest tile, the accumulators rescaled
 // (exactly) when T changes and unscaled once at the end.
-template <int D, bool MASK_IN, bool NB, bool BF = false, bool MB = false, bool X0 = false, bool F16 = false>
+// SKIP (lg_gcn_bwd_nm_skip, the residual trunk x_out = x + f(x)): dx = t W + dy_own.  The own
+// dy rows are added where the dx tile comes back from LDS in the row layout, one fp32 add per
+// element after the product; the input mask (mask_out) and the node-bias sum then act on the
+// summed dx, in that layout too (the x tile is still in LDS).
+template <int D, bool MASK_IN, bool NB, bool BF = false, bool MB = false, bool X0 = false, bool F16 = false,
+          bool SKIP = false>
 __global__ void __launch_bounds__(64 * kNmBwdWaves3, 2)
 k_gcn_bwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, const float* __restrict__ dy,
               const float* __restrict__ yv, const float* __restrict__ x, const float* __restrict__ W,
@@ -1343,6 +1373,7 @@ k_gcn_bwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, c
               uint32_t B, uint32_t ngroups, lg_fastdiv fdN, int mask_out, float scale_in, float scale_out,
               const uint16_t* __restrict__ ymask, NbX0 x0) {
     static_assert(!MB || MASK_IN, "mask bits replace the y gather of MASK_IN");
+    static_assert(!SKIP || (MB && !X0 && !BF), "the skip reads its branch mask as bits, dense fp32 tier");
     constexpr bool MY = MASK_IN && !MB;  // mask from gathered y rows
     using G = NmGeo<D>;
     using LY = Nb3Lds<D, MASK_IN>;
@@ -1572,6 +1603,7 @@ k_gcn_bwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, c
     f32x4 nbacc[NB ? G::CH : 1];              // NB: channels 16mt + 4q + reg over this lane's rows j
 #pragma unroll
     for (int mt = 0; mt < (NB ? G::CH : 1); ++mt) nbacc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 nbrow = f32x4{0.f, 0.f, 0.f, 0.f};  // SKIP && NB: the same sum in the row layout (dbacc's)
 
     for (int32_t tile = tfirst; tile < tend; tile += tstride) {
         const uint32_t n = cn, b0 = cb0;
@@ -1800,6 +1832,7 @@ k_gcn_bwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, c
             __builtin_amdgcn_sched_barrier(0);
         }
         }
+        if constexpr (!SKIP) {
         if (mask_out & 1) {
 #pragma unroll
             for (int mt = 0; mt < G::CH; ++mt) {
@@ -1816,6 +1849,7 @@ k_gcn_bwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, c
                 if (mask_out & 2) continue;
             }
         }
+        }
         wave_sync_nm();
 #pragma unroll
         for (int mt = 0; mt < G::CH; ++mt) st4(tl + tix(j, 4 * mt + q), o[mt]);
@@ -1824,6 +1858,24 @@ k_gcn_bwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, c
         f32x4 vk[G::K];
 #pragma unroll
         for (int k = 0; k < G::K; ++k) vk[k] = ld4(tl + tix(G::RPI * k + rl, fg));
+        if constexpr (SKIP) {
+#pragma unroll
+            for (int k = 0; k < G::K; ++k) {
+                vk[k] = vk[k] + ld(dys, tlo[k] + ob);  // dx = t W + dy_own
+                if (mask_out & 1) {
+                    const f32x4 xm = ld4(xl + tix(G::RPI * k + rl, fg));
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) vk[k][c] = xm[c] > 0.f ? vk[k][c] * scale_out : 0.f;
+                }
+            }
+            if constexpr (NB) {
+                if (node_slot[n] < 0) {
+#pragma unroll
+                    for (int k = 0; k < G::K; ++k) nbrow += vk[k];
+                    if (mask_out & 2) continue;
+                }
+            }
+        }
 #pragma unroll
         for (int k = 0; k < G::K; ++k)
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) uint32_t, vk[k]),
@@ -1847,7 +1899,12 @@ k_gcn_bwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, c
 #pragma unroll
             for (int b = 0; b < G::CH; ++b) dw[a][b] = (dw[a][b] * r1) * r2;
     }
-    if constexpr (NB) {  // fold the 16 row lanes j of each (q, reg)
+    if constexpr (NB && SKIP) {
+#pragma unroll
+        for (int off = G::LPR; off < 64; off <<= 1)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) nbrow[i] += __shfl_xor(nbrow[i], off);
+    } else if constexpr (NB) {  // fold the 16 row lanes j of each (q, reg)
 #pragma unroll
         for (int off = 1; off < 16; off <<= 1)
 #pragma unroll
@@ -1876,11 +1933,14 @@ k_gcn_bwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, c
             if (lane < G::LPR)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) red[D * D + 4 * lane + i] += dbacc[i];
-            if (NB && j == 0)
+            if (NB && !SKIP && j == 0)
 #pragma unroll
                 for (int mt = 0; mt < G::CH; ++mt)
 #pragma unroll
                     for (int i = 0; i < 4; ++i) red[D * D + D + 16 * mt + 4 * q + i] += nbacc[mt][i];
+            if (NB && SKIP && lane < G::LPR)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) red[D * D + D + 4 * lane + i] += nbrow[i];
         }
     }
     __syncthreads();
@@ -2312,6 +2372,11 @@ auto nm3_kernel(int flags) {
     if (flags & LG_F_BF16) return k_gcn_fwd_nm3<D, DR, RL, true, 4, true>;
     return (flags & LG_F_F32_MFMA) ? k_gcn_fwd_nm3<D, DR, RL, false, 4> : k_gcn_fwd_nm3<D, DR, RL, true, 4>;
 }
+template <int D, bool DR, bool RL>
+auto pc_skip_kernel(bool f16) {
+    return f16 ? k_gcn_fwd_pc<D, DR, RL, false, true, kPcProdN, kPcNC, false, true>
+               : k_gcn_fwd_pc<D, DR, RL, false, false, kPcProdN, kPcNC, false, true>;
+}
 template <int D, bool DR, bool RL, bool X0>
 auto pc_kernel(bool bf16, bool f16) {
     return bf16 ? k_gcn_fwd_pc<D, DR, RL, true, false, kPcProdN, kPcNC, X0>
@@ -2319,10 +2384,13 @@ auto pc_kernel(bool bf16, bool f16) {
                        : k_gcn_fwd_pc<D, DR, RL, false, false, kPcProdN, kPcNC, X0>);
 }
 
-// lg_gcn_fwd_nm_bits (x0 == NULL) and lg_gcn_fwd_nm_x0 (x the sensor rows, *x0 the rest)
+// lg_gcn_fwd_nm_bits (x0 == NULL), lg_gcn_fwd_nm_x0 (x the sensor rows, *x0 the rest) and
+// lg_gcn_fwd_nm_skip (skip: y = x + the layer, on k_gcn_fwd_pc's fp32 forms only)
 int nm_fwd(const int32_t* nodetab, const int32_t* pairs, const float* x, const float* W, const float* bias, float* y,
            int64_t B, int64_t N, int64_t D, int flags, float dropout_p, uint64_t seed, uint32_t salt,
-           lg_stream_t stream, uint16_t* ymask, const PcX0* x0) {
+           lg_stream_t stream, uint16_t* ymask, const PcX0* x0, bool skip = false) {
+    if (skip && (x0 || !ymask)) return LG_EINVAL;
+    if (skip && (flags & (LG_F_BF16 | LG_F_NM3 | LG_F_F32_MFMA))) return LG_EUNSUPPORTED;
     if (B < 0 || N <= 0 || !nodetab || !pairs || !x || !W || !y || x == y) return LG_EINVAL;
     if ((flags & LG_F_BIAS) && !bias) return LG_EINVAL;
     const bool drop = (flags & LG_F_DROPOUT) != 0;
@@ -2352,7 +2420,14 @@ int nm_fwd(const int32_t* nodetab, const int32_t* pairs, const float* x, const f
     auto launch = [&](auto dc, auto drc) {
         constexpr int DD = decltype(dc)::value;
         constexpr bool DR = decltype(drc)::value;
-        if (nm3) {
+        if (skip) {
+            auto kern = relu ? pc_skip_kernel<DD, DR, true>(f16) : pc_skip_kernel<DD, DR, false>(f16);
+            const size_t dyn = PcLds<DD, kPcProdN, kPcNC>::BYTES;
+            const int thr = 64 * kPcProdN * (1 + kPcNC);
+            const int grid = nm_grid(kern, thr, dyn, ntiles, 4, 1);
+            lg_launch(kern, grid, thr, dyn, s, nodetab, pr, x, W, bp, y, N32, B32, G32, fd, dropout_p, scale, seed,
+                      salt, ymask, xz);
+        } else if (nm3) {
             auto kern = relu ? nm3_kernel<DD, DR, true>(flags) : nm3_kernel<DD, DR, false>(flags);
             const size_t dyn = (flags & LG_F_F32_MFMA) && !bf16 ? Nm3Lds<DD, false, 4>::BYTES : Nm3Lds<DD, true, 4>::BYTES;
             const int grid = nm_grid(kern, 64 * 4, dyn, ntiles, 4, 3);
@@ -2390,6 +2465,14 @@ extern "C" int lg_gcn_fwd_nm_bits(const int32_t* nodetab, const int32_t* pairs, 
                              float dropout_p, uint64_t seed, uint32_t salt, lg_stream_t stream, uint16_t* ymask) {
     (void)nnz_cap;
     return nm_fwd(nodetab, pairs, x, W, bias, y, B, N, D, flags, dropout_p, seed, salt, stream, ymask, nullptr);
+}
+
+extern "C" int lg_gcn_fwd_nm_skip(const int32_t* nodetab, const int32_t* pairs, const float* x, const float* W,
+                                  const float* bias, float* y, int64_t B, int64_t N, int64_t D, int64_t nnz_cap,
+                                  int flags, float dropout_p, uint64_t seed, uint32_t salt, lg_stream_t stream,
+                                  uint16_t* ymask) {
+    (void)nnz_cap;
+    return nm_fwd(nodetab, pairs, x, W, bias, y, B, N, D, flags, dropout_p, seed, salt, stream, ymask, nullptr, true);
 }
 
 extern "C" int lg_gcn_fwd_nm_x0(const int32_t* nodetab_s, const int32_t* pairs_s, const float* xs0,
@@ -2438,7 +2521,9 @@ namespace {
 int nm_bwd(const int32_t* nodetab_t, const int32_t* pairs_t, const float* dy, const float* y, const float* x,
            const float* W, float* dx_out, float* dW, float* db, const int32_t* node_slot, float* dnode_bias, int64_t B,
            int64_t N, int64_t D, int flags, float scale_in, float scale_out, void* workspace, int64_t ws_bytes,
-           lg_stream_t stream, const uint16_t* ymask, const NbX0* x0) {
+           lg_stream_t stream, const uint16_t* ymask, const NbX0* x0, bool skip = false) {
+    if (skip && (x0 || !ymask || !(flags & LG_F_MASK_IN) || dy == dx_out)) return LG_EINVAL;
+    if (skip && (flags & LG_F_BF16)) return LG_EUNSUPPORTED;
     if (B < 0 || N <= 0 || !nodetab_t || !pairs_t || !dy || !x || !W || !dx_out || !dW || !workspace) return LG_EINVAL;
     if ((node_slot == nullptr) != (dnode_bias == nullptr)) return LG_EINVAL;
     const bool mask_in = (flags & LG_F_MASK_IN) != 0;
@@ -2495,8 +2580,21 @@ int nm_bwd(const int32_t* nodetab_t, const int32_t* pairs_t, const float* dy, co
             else LG_NM_BWD(DD, false, false);            \
         }                                                \
     } while (0)
-    if (D == 64) LG_NM_BWD_D(64);
+#define LG_NM_BWD_S(DD, NBB)                                                                     \
+    launch(f16 ? k_gcn_bwd_nm3<DD, true, NBB, false, true, false, true, true>                    \
+               : k_gcn_bwd_nm3<DD, true, NBB, false, true, false, false, true>,                  \
+           Nb3Lds<DD, true>::BYTES)
+    if (skip) {
+        if (D == 64) {
+            if (node_slot) LG_NM_BWD_S(64, true);
+            else LG_NM_BWD_S(64, false);
+        } else {
+            if (node_slot) LG_NM_BWD_S(32, true);
+            else LG_NM_BWD_S(32, false);
+        }
+    } else if (D == 64) LG_NM_BWD_D(64);
     else LG_NM_BWD_D(32);
+#undef LG_NM_BWD_S
 #undef LG_NM_BWD_D
 #undef LG_NM_BWD
 #undef LG_NM_BWD_P
@@ -2514,6 +2612,15 @@ extern "C" int lg_gcn_bwd_nm_bits(const int32_t* nodetab_t, const int32_t* pairs
                              const uint16_t* ymask) {
     return nm_bwd(nodetab_t, pairs_t, dy, y, x, W, dx_out, dW, db, node_slot, dnode_bias, B, N, D, flags, scale_in,
                   scale_out, workspace, ws_bytes, stream, ymask, nullptr);
+}
+
+extern "C" int lg_gcn_bwd_nm_skip(const int32_t* nodetab_t, const int32_t* pairs_t, const float* dy, const float* y,
+                                  const float* x, const float* W, float* dx_out, float* dW, float* db,
+                                  const int32_t* node_slot, float* dnode_bias, int64_t B, int64_t N, int64_t D,
+                                  int flags, float scale_in, float scale_out, void* workspace, int64_t ws_bytes,
+                                  lg_stream_t stream, const uint16_t* ymask) {
+    return nm_bwd(nodetab_t, pairs_t, dy, y, x, W, dx_out, dW, db, node_slot, dnode_bias, B, N, D, flags, scale_in,
+                  scale_out, workspace, ws_bytes, stream, ymask, nullptr, true);
 }
 
 extern "C" int lg_gcn_bwd_nm_x0(const int32_t* nodetab_t, const int32_t* pairs_t, const int32_t* pos_slot_t,

@@ -35,6 +35,13 @@ link's two directed edges, through PyG's weighted gcn_norm (lg_graph_build_w).  
 are a buffer (`edge_weight`); learned ones a parameter `edge_log_weight` = log of the link
 weight, whose gradient comes through the trunk ops' edge_w input (library._layer_dw,
 lg_sddmm_nm).  With neither, nothing differs from the unweighted detector.
+
+Residual trunk (LeakDetector(..., gnn_layers=N, skip="residual"); not in the reference): every
+GCN layer is x = x + dropout(relu(conv(x))), the form deep GCNs are trained in (a non-sensor
+node sees only sensors within gnn_layers hops: utils.sensor_reach).  The skip runs on the
+fp32-tier node-major kernels (lg_gcn_fwd_nm_skip / lg_gcn_bwd_nm_skip) at every batch size,
+through the unfused route: the encoder module, then leakgnn::gnn_trunk with x_0 materialised.
+skip="none" (the default) is the detector as before, bit for bit.
 """
 from __future__ import annotations
 
@@ -165,13 +172,22 @@ class LeakDetector(nn.Module):
                  sensor_hidden: int = 64, node_hidden: int = 64, gnn_layers: int = 2, dropout: float = 0.1,
                  use_time: bool = True, include_links: Sequence[str] = ("PIPES", "PUMPS", "VALVES"),
                  mlp_dtype: str = "fp32", sensor_layers: int = 1, sensor_dropout: float = 0.0,
-                 edge_weight: Optional[torch.Tensor] = None, learn_edge_weight: bool = False) -> None:
+                 edge_weight: Optional[torch.Tensor] = None, learn_edge_weight: bool = False,
+                 skip: str = "none") -> None:
         """edge_weight: None, or a positive floating (n_links,) tensor, one weight per link in the
         order of the link table build_wdn_graph_from_inp walks (utils.link_edge_weights builds one
         from the .inp file); link j is the directed edges 2j and 2j + 1 of edge_index_single.
         learn_edge_weight: the link weights are learned, exp(edge_log_weight), starting from
-        edge_weight (or 1)."""
+        edge_weight (or 1).
+        skip: "none", or "residual": every GCN layer x = x + dropout(relu(conv(x))).  An attribute
+        like mlp_dtype: no parameter, no state-dict entry."""
         super().__init__()
+        if skip not in ("none", "residual"):
+            raise ValueError(f"skip must be 'none' or 'residual', got {skip!r}")
+        if skip == "residual" and mlp_dtype == "bf16":
+            raise NotImplementedError("skip='residual' needs mlp_dtype='fp32': the skip lives on the fp32-tier "
+                                      "trunk kernels (lg_gcn_fwd_nm_skip / lg_gcn_bwd_nm_skip) only")
+        self.skip = skip
         if mlp_dtype not in ("fp32", "bf16"):
             raise ValueError(f"mlp_dtype must be 'fp32' or 'bf16', got {mlp_dtype!r}")
         if learn_edge_weight and mlp_dtype == "bf16":
@@ -330,6 +346,8 @@ class LeakDetector(nn.Module):
         g = self.sensor_encoder.gru
         if not (self.fuse_encoder and g.num_layers == 1 and g.bias and not g.bidirectional):
             return False
+        if self.skip != "none":  # the skip is not folded into encoder_trunk and the X0 kernels
+            return False
         if self.capture is not None:  # the capture reads h_s, which the fused op never forms
             return False
         if residual.requires_grad or (tfeat is not None and self.sensor_encoder.use_time and tfeat.requires_grad):
@@ -375,7 +393,8 @@ class LeakDetector(nn.Module):
                 self._batched_weights[(B, dev)] = hit
             ew = hit[1]
         for conv in self.convs:
-            x = F.dropout(F.relu(conv(x, ei) if ew is None else conv(x, ei, ew)), p, self.training)
+            br = F.dropout(F.relu(conv(x, ei) if ew is None else conv(x, ei, ew)), p, self.training)
+            x = x + br if self.skip == "residual" else br
         h_nodes = x.view(B, N, -1)
         ends = inc.ends.long()
         pipe_logits = self.edge_head(h_nodes[:, ends[:, 0]], h_nodes[:, ends[:, 1]])     # (B, P)
@@ -392,7 +411,9 @@ class LeakDetector(nn.Module):
         f = ops._f32
         Wn, bn = f(self.sensor_to_node.weight), f(self.sensor_to_node.bias)  # (D, Ds+1), (D,)
         N, D = len(self.node_names), Wn.shape[0]
-        nm = ops.use_node_major(B, N, D, bf16=self.mlp_dtype == "bf16")
+        skip = self.skip == "residual"
+        # a skip model takes the node-major layout at every B, as the bf16 tier does
+        nm = ops.use_node_major(B, N, D, bf16=self.mlp_dtype == "bf16" or skip)
         drop = self.training and float(self.dropout.p) > 0.0
         g = graph
         bf16 = self.mlp_dtype == "bf16"
@@ -426,16 +447,17 @@ class LeakDetector(nn.Module):
                     h_s.retain_grad()
                 self.capture["h_s"] = h_s
             # sensor_to_node (rows with a sensor: [h_s, 1] W^T + b; without: b) folded into node init
-            mk = self._x0marks(g, slot) if (nm and self.compress_x0 and len(self.convs) > 1) else None
+            mk = self._x0marks(g, slot) if (nm and self.compress_x0 and len(self.convs) > 1 and not skip) else None
             out_t = torch.ops.leakgnn.gnn_trunk(
                 h_s, Wn, bn, [f(c.lin.weight) for c in self.convs], [f(c.bias) for c in self.convs], slot, sensor_idx,
                 nonsensor, slot_live, g.nodetab, g.pairs, g.rowptr, g.col, g.w, g.nodetab_t, g.pairs_t, g.rowptr_t,
                 g.col_t, g.w_t, float(self.dropout.p) if drop else 0.0, nm,
                 library.seed_tensor(residual.device) if drop else _NO_SEED,
                 mk.nodetab_s if mk is not None else None, mk.pairs_s if mk is not None else None,
-                mk.pos_slot_t if mk is not None else None, edge_w, bf16=bf16)
+                mk.pos_slot_t if mk is not None else None, edge_w, bf16=bf16, **({"skip": True} if skip else {}))
             xs = out_t[:-2]                     # [x_0 .. x_L] (then x_L's mask bits and x_0's, when compressed)
             x0bits = out_t[-1]
+            ymask = out_t[-2]
         h_nodes = xs[-1]                                                   # (N, B, D) node-major, else (B, N, D)
         if self.keep_boundary:
             self.boundary = h_nodes
@@ -455,10 +477,26 @@ class LeakDetector(nn.Module):
             if x0bits.numel() > 0:  # x_0 compressed: materialise it for the diagnostics
                 xs = [library.expand_x0(xs[0], x0bits, slot, bn, N, float(self.dropout.p) if drop else 0.0)] + xs[1:]
             self.capture.update(xs=xs, node_major=nm, edge_hidden=out[1], noleak_hidden=out[3])
+            if skip:  # the branches' keep decisions [f > 0], which xs[l] > 0 no longer is
+                nl = len(self.convs)
+                self.capture["fmask"] = [_unpack_mask(w, N, B, D) for w in ymask.view(nl, -1)] if nl else []
         return out[0]
 
 
 _NO_SEED = torch.zeros(1, dtype=torch.long)  # seed argument of an op that draws no dropout mask
+
+
+def _unpack_mask(words: torch.Tensor, N: int, B: int, D: int) -> torch.Tensor:
+    """The mask words of lg_gcn_fwd_nm_bits / _skip (include/leakgnn.h) as a bool (N, B, D) tensor:
+    per node and 16-window tile 64 lanes, bit 4k + i of lane l = row 16g + (64 / (D/4)) k + l // (D/4),
+    channel 4 (l % (D/4)) + i.  Diagnostics only (LeakDetector.capture)."""
+    T, lpr = (B + 15) // 16, D // 4
+    rpp = 64 // lpr
+    w = words.view(N, T, rpp, lpr).to(torch.int32) & 0xFFFF                     # [n][g][l // lpr][l % lpr]
+    sh = (4 * torch.arange(16 // rpp, device=words.device).view(-1, 1) + torch.arange(4, device=words.device)).view(-1)
+    bits = ((w.unsqueeze(-1) >> sh.to(torch.int32)) & 1).bool()                 # [n][g][lr][lc][k * 4 + i]
+    bits = bits.view(N, T, rpp, lpr, 16 // rpp, 4).permute(0, 1, 4, 2, 3, 5)   # [n][g][k][lr][lc][i]
+    return bits.reshape(N, T * 16, D)[:, :B].contiguous()
 
 
 def detector_from_args(inp_path: str | Path, sensor_ids: Sequence[str], pipe_ids_in_order: Sequence[str],
@@ -467,13 +505,17 @@ def detector_from_args(inp_path: str | Path, sensor_ids: Sequence[str], pipe_ids
     two layers, dropout 0.1), its edge-weight options read from `args`: the CLI's vars(namespace)
     or a checkpoint's ckpt["args"].  "edge_weight" in {none, ones, length, inv_length, conductance}
     (utils.link_edge_weights) and "learn_edge_weight"; a missing key is the unweighted detector.
+    "gnn_layers" (default 2) and "skip" in {none, residual} (default none): a missing key is the
+    two-layer plain trunk, so checkpoints from before these flags load as before.
     cls: the class to build (the caller's own LeakDetector name; default: this module's)."""
     args = args or {}
     mode = args.get("edge_weight") or "none"
     ew = link_edge_weights(inp_path, mode=mode) if mode != "none" else None
+    skip = args.get("skip") or "none"
     return (cls or LeakDetector)(inp_path, sensor_ids, pipe_ids_in_order, sensor_hidden=64, node_hidden=64,
-                                 gnn_layers=2, dropout=0.1, use_time=True, edge_weight=ew,
-                                 learn_edge_weight=bool(args.get("learn_edge_weight", False)), **kwargs)
+                                 gnn_layers=int(args.get("gnn_layers") or 2), dropout=0.1, use_time=True,
+                                 edge_weight=ew, learn_edge_weight=bool(args.get("learn_edge_weight", False)),
+                                 **({"skip": skip} if skip != "none" else {}), **kwargs)
 
 
 def detector_from_checkpoint(ckpt: dict, inp_path: str | Path, **kwargs) -> LeakDetector:

@@ -1096,7 +1096,7 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
               nodetab: Tensor, pairs: Tensor, rowptr: Tensor, col: Tensor, w: Tensor, nodetab_t: Tensor,
               pairs_t: Tensor, rowptr_t: Tensor, col_t: Tensor, w_t: Tensor, p: float, node_major: bool, seed: Tensor,
               nodetab_s: Optional[Tensor], pairs_s: Optional[Tensor], pos_slot_t: Optional[Tensor],
-              edge_w: Optional[Tensor] = None, *, bf16: bool = False) -> List[Tensor]:
+              edge_w: Optional[Tensor] = None, *, bf16: bool = False, skip: bool = False) -> List[Tensor]:
     """[x_0, ..., x_L, ymask, x0bits]: sensor_to_node + node init (detector.py:160, 178-190),
     then L x dropout(relu(GCNConv)).
 
@@ -1117,7 +1117,12 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
     edge_w: the graph's normalised coefficients `w` carrying an autograd edge (learned edge
     weights, leakgnn::gcn_edge_norm), or None.  An autograd anchor only: the kernels read the
     tables, which hold the same numbers; when it requires grad the backward returns dL/dw
-    (_layer_dw: lg_sddmm_nm per layer)."""
+    (_layer_dw: lg_sddmm_nm per layer).
+    skip (keyword-only: the dispatcher drops positional defaults): identity skips,
+      x_{l+1} = x_l + dropout(relu(Ahat x_l W_l^T + b_l))                  (lg_gcn_fwd_nm_skip)
+    on the node-major fp32 tier with the dense node init.  [x_{l+1} > 0] is then no longer the
+    branch's ReLU/dropout mask, so EVERY layer keeps its [f > 0] bits: ymask is (L * nmask,),
+    layer l's words at [l * nmask, (l + 1) * nmask) (each 1/32 of an activation)."""
     lib = load_library()
     h_s, proj_weight, node_bias = _c(h_s), _c(proj_weight), _c(node_bias)
     weights, biases = [_c(t) for t in weights], [_c(t) for t in biases]
@@ -1127,6 +1132,8 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
     _check_d(D)
     if bf16 and not node_major:  # the window-major kernels have no bf16 form (ops.use_node_major)
         raise ValueError("gnn_trunk: the bf16 tier runs on the node-major layout only")
+    if skip and (bf16 or not node_major):
+        raise ValueError("gnn_trunk: skip=True runs on the node-major fp32 tier only")
     if tuple(proj_weight.shape) != (D, Ds + 1):
         raise ValueError(f"proj_weight must be (D, Ds + 1) = ({D}, {Ds + 1}), got {tuple(proj_weight.shape)}")
     N = sensor_slot.shape[0]
@@ -1136,7 +1143,7 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
     st = stream_of(h_s)
     L = len(weights)
     nmask = N * ((B + 15) // 16) * 64
-    x0c = _compress_x0(nodetab_s, node_major, L)
+    x0c = _compress_x0(nodetab_s, node_major, L) and not skip
     if x0c:
         x0 = torch.empty((S, B, D), device=h_s.device, dtype=torch.float32)
         x0bits = torch.empty(nmask, device=h_s.device, dtype=torch.int16)
@@ -1153,7 +1160,8 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
                                             dflag | (nat.LG_F_NODE_MAJOR if node_major else 0), p, seed_v, 0 | sbit, st),
                   "lg_node_init_proj_fwd")
     xs = [x0]
-    ymask = torch.empty(nmask if (node_major and L > 0) else 0, device=h_s.device, dtype=torch.int16)
+    ymask = torch.empty((nmask * (L if skip else 1)) if (node_major and L > 0) else 0, device=h_s.device,
+                        dtype=torch.int16)
     for l, (W, b) in enumerate(zip(weights, biases)):
         y = torch.empty((N, B, D), device=h_s.device, dtype=torch.float32) if node_major else torch.empty_like(x0)
         flags = nat.LG_F_BIAS | nat.LG_F_RELU | dflag | (nat.LG_F_BF16 if bf16 else 0)
@@ -1162,6 +1170,11 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
                 check(lib.lg_gcn_fwd_nm_x0(ptr(nodetab_s), ptr(pairs_s), ptr(x0), ptr(x0bits), ptr(node_bias),
                                            ptr(W), ptr(b), ptr(y), B, N, S, D, flags | GCN_FWD_NM_EXTRA_FLAGS, p,
                                            seed_v, (l + 1) | sbit, st), "lg_gcn_fwd_nm_x0")
+            elif skip:
+                check(lib.lg_gcn_fwd_nm_skip(ptr(nodetab), ptr(pairs), ptr(xs[-1]), ptr(W), ptr(b), ptr(y), B, N,
+                                             D, col.numel(), flags | (GCN_FWD_NM_EXTRA_FLAGS & nat.LG_F_BF16X3), p,
+                                             seed_v, (l + 1) | sbit, st, ptr(ymask[l * nmask:(l + 1) * nmask])),
+                      "lg_gcn_fwd_nm_skip")
             elif node_major:
                 fx = GCN_FWD_DENSE_EXTRA_FLAGS if not bf16 else 0
                 check(lib.lg_gcn_fwd_nm_bits(ptr(nodetab), ptr(pairs), ptr(xs[-1]), ptr(W), ptr(b), ptr(y), B, N,
@@ -1178,16 +1191,17 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
 @gnn_trunk.register_fake
 def _(h_s, proj_weight, node_bias, weights, biases, sensor_slot, sensor_idx, nonsensor_idx, slot_live, nodetab, pairs,
       rowptr, col, w, nodetab_t, pairs_t, rowptr_t, col_t, w_t, p, node_major, seed, nodetab_s, pairs_s, pos_slot_t,
-      edge_w=None, *, bf16=False):
+      edge_w=None, *, bf16=False, skip=False):
     B, S = h_s.shape[0], h_s.shape[1]
     D = proj_weight.shape[0]
     N = sensor_slot.shape[0]
     shape = (N, B, D) if node_major else (B, N, D)
     L = len(weights)
     nmask = N * ((B + 15) // 16) * 64 if (node_major and L > 0) else 0
-    x0c = _compress_x0(nodetab_s, node_major, L)
+    x0c = _compress_x0(nodetab_s, node_major, L) and not skip
     x0 = h_s.new_empty((S, B, D)) if x0c else h_s.new_empty(shape)
-    return ([x0] + [h_s.new_empty(shape) for _ in range(L)] + [h_s.new_empty((nmask,), dtype=torch.int16)]
+    return ([x0] + [h_s.new_empty(shape) for _ in range(L)]
+            + [h_s.new_empty((nmask * (L if skip else 1),), dtype=torch.int16)]
             + [h_s.new_empty((nmask if x0c else 0,), dtype=torch.int16)])
 
 
@@ -1198,7 +1212,7 @@ def gnn_trunk_backward(grad_out: Tensor, xs: List[Tensor], ymask: Tensor, h_s: T
                        nodetab_t: Tensor, pairs_t: Tensor, rowptr_t: Tensor, col_t: Tensor, w_t: Tensor, p: float,
                        node_major: bool, x0bits: Optional[Tensor], x0_bias: Optional[Tensor],
                        pos_slot_t: Optional[Tensor], rowptr: Optional[Tensor] = None, col: Optional[Tensor] = None,
-                       *, bf16: bool = False
+                       *, bf16: bool = False, skip: bool = False
                        ) -> Tuple[Tensor, Tensor, Tensor, List[Tensor], List[Tensor], Tensor]:
     """(dh_s, dproj_weight, dnode_bias, [dW_l], [db_l], dw): one fused lg_gcn_bwd[_nm] per layer,
     last first (ReLU/dropout masks of a layer's output and input applied inside the kernel
@@ -1207,7 +1221,9 @@ def gnn_trunk_backward(grad_out: Tensor, xs: List[Tensor], ymask: Tensor, h_s: T
     dh_s, dW and the full bias gradient).  x0bits, x0_bias (the node init's bias), pos_slot_t: x_0 is
     compressed (gnn_trunk's x0marks path; xs[0] its sensor rows) and layer 0's backward reads
     it through lg_gcn_bwd_nm_x0.  rowptr, col (the FORWARD CSR): the edge coefficients learn, and
-    dw is dL/dw over its slots (sum over the layers of _layer_dw); otherwise dw is empty."""
+    dw is dL/dw over its slots (sum over the layers of _layer_dw); otherwise dw is empty.
+    skip: gnn_trunk's identity skips (lg_gcn_bwd_nm_skip per layer, every layer's mask from its own
+    words of ymask)."""
     lib = load_library()
     L = len(weights)
     dev = grad_out.device
@@ -1231,15 +1247,15 @@ def gnn_trunk_backward(grad_out: Tensor, xs: List[Tensor], ymask: Tensor, h_s: T
                                                   nonsensor_idx, slot_live, nodetab_t, pairs_t, rowptr_t, col_t, w_t,
                                                   node_major, bf16, scale, wss, dWs, dbs, dbias_ns, st,
                                                   (x0bits, x0_bias, pos_slot_t) if x0bits is not None else None, p,
-                                                  wgrad)
+                                                  wgrad, skip)
     return dh_s, dWp, dbp, dWs, dbs, (wgrad.total(dev) if wgrad is not None else torch.empty(0, device=dev))
 
 
 def _trunk_backward_launches(lib, dy, xs, ymask, h_s, proj_weight, weights, sensor_slot, sensor_idx, nonsensor_idx, slot_live,
                              nodetab_t, pairs_t, rowptr_t, col_t, w_t, node_major, bf16, scale, wss, dWs, dbs, dbias_ns,
-                             st, x0c=None, p=0.0, wgrad=None):
+                             st, x0c=None, p=0.0, wgrad=None, skip=False):
     dy = _trunk_layer_launches(lib, dy, xs, ymask, weights, sensor_slot, nodetab_t, pairs_t, rowptr_t, col_t, w_t,
-                               node_major, bf16, scale, wss, dWs, dbs, dbias_ns, st, x0c, p, wgrad)
+                               node_major, bf16, scale, wss, dWs, dbs, dbias_ns, st, x0c, p, wgrad, skip)
     L = len(weights)
     dev = dy.device
     if node_major:
@@ -1279,15 +1295,20 @@ class _WGrad:
 
 
 def _layer_dw(dy: Tensor, xs, ymask: Tensor, W: Tensor, l: int, L: int, node_major: bool, scale: float,
-              rowptr: Tensor, col: Tensor, x0c, sensor_slot: Tensor, p: float) -> Tensor:
+              rowptr: Tensor, col: Tensor, x0c, sensor_slot: Tensor, p: float, skip: bool = False) -> Tensor:
     """Layer l's share of dL/dw: G_l[k] = sum_b (dz W_l)[n, b] . x_l[col k, b] for every slot k of
     row n, with dz = dy * scale * [x_{l+1} > 0] on the last layer and dz = dy on the others (their dy
     is the layer above's dx, which that launch already masked: LG_F_MASK_OUT), exactly the dz of
     the layer's own backward launch.  Node-major: lg_sddmm_nm (the last layer's mask from the bit
     words when the forward wrote them); the compressed node init is materialised for layer 0
     (lg_node_init_expand; a compressed-x0 form of the kernel is left for later).  Window-major:
-    da on a library GEMM, then ONE lg_sddmm_cols over the [N][B * D] transposes.  Deterministic."""
+    da on a library GEMM, then ONE lg_sddmm_cols over the [N][B * D] transposes.  Deterministic.
+    skip: dy is the gradient of x_{l+1} = x_l + f_l, no launch masked it, and every layer's dz is
+    dy * scale * [f_l > 0] from the layer's own words of ymask."""
     last = l == L - 1
+    if skip:
+        nmask = ymask.numel() // L
+        return sddmm_nm(rowptr, col, dy, W, xs[l], ymask=ymask[l * nmask:(l + 1) * nmask], mask_in=True, scale=scale)
     if node_major:
         x = xs[l]
         if x0c is not None and l == 0:
@@ -1305,11 +1326,13 @@ def _layer_dw(dy: Tensor, xs, ymask: Tensor, W: Tensor, l: int, L: int, node_maj
 
 
 def _trunk_layer_launches(lib, dy, xs, ymask, weights, sensor_slot, nodetab_t, pairs_t, rowptr_t, col_t, w_t, node_major,
-                          bf16, scale, wss, dWs, dbs, dbias_ns, st, x0c=None, p=0.0, wgrad=None) -> Tensor:
+                          bf16, scale, wss, dWs, dbs, dbias_ns, st, x0c=None, p=0.0, wgrad=None, skip=False) -> Tensor:
     """The GCN layers' backward, last first; returns the node init's pre-activation gradient
     (layer 0's dx: masked by the node init's ReLU / dropout; node-major with the compressed
     node init: the sensor nodes' rows only) and leaves the non-sensor rows' sum in dbias_ns.
-    wgrad (_WGrad): every layer also adds its dL/dw (_layer_dw)."""
+    wgrad (_WGrad): every layer also adds its dL/dw (_layer_dw).
+    skip: x_{l+1} = x_l + f_l, so dx_l = dx_{l+1} + (branch); every layer applies its own mask
+    (LG_F_MASK_IN on its bit words) and only layer 0 a LG_F_MASK_OUT, the node init's."""
     L = len(weights)
     dev = dy.device
     if node_major:
@@ -1319,6 +1342,8 @@ def _trunk_layer_launches(lib, dy, xs, ymask, weights, sensor_slot, nodetab_t, p
     for l in range(L - 1, -1, -1):
         ws = wss[l]
         flags = nat.LG_F_MASK_OUT | (nat.LG_F_MASK_IN if l == L - 1 else 0) | (nat.LG_F_BF16 if bf16 else 0)
+        if skip:
+            flags = nat.LG_F_MASK_IN | (nat.LG_F_MASK_OUT if l == 0 else 0)
         if node_major and not bf16:
             flags |= GCN_BWD_NM_EXTRA_FLAGS
         if l == 0:  # lg_sensor_proj_bwd reads only the sensor rows of layer 0's dx
@@ -1329,7 +1354,7 @@ def _trunk_layer_launches(lib, dy, xs, ymask, weights, sensor_slot, nodetab_t, p
         slot_p, dbias_p = (ptr(sensor_slot), ptr(dbias_ns)) if l == 0 else (None, None)
         if wgrad is not None:
             wgrad.add(_layer_dw(dy, xs, ymask, weights[l], l, L, node_major, scale, wgrad.rowptr, wgrad.col, x0c,
-                                sensor_slot, p))
+                                sensor_slot, p, skip))
         with _timed("gcn_bwd" if l == L - 1 else f"gcn_bwd_l{l}", dev):
             if x0c is not None and l == 0:  # the compressed node init (xs[0]: its sensor rows, (S, B, D))
                 x0bits, node_bias, pos_slot_t = x0c
@@ -1338,6 +1363,12 @@ def _trunk_layer_launches(lib, dy, xs, ymask, weights, sensor_slot, nodetab_t, p
                                            ptr(x0bits), ptr(node_bias), ptr(weights[0]), ptr(dx), ptr(dW), ptr(db),
                                            slot_p, dbias_p, B, N, S, D, flags | (nat.LG_F_DROPOUT if p > 0.0 else 0),
                                            p, scale, ptr(ws), ws.numel(), st), "lg_gcn_bwd_nm_x0")
+            elif skip:
+                nmask = ymask.numel() // L
+                check(lib.lg_gcn_bwd_nm_skip(ptr(nodetab_t), ptr(pairs_t), ptr(dy), None, ptr(xs[l]),
+                                             ptr(weights[l]), ptr(dx), ptr(dW), ptr(db), slot_p, dbias_p, B, N, D,
+                                             flags, scale, scale, ptr(ws), ws.numel(), st,
+                                             ptr(ymask[l * nmask:(l + 1) * nmask])), "lg_gcn_bwd_nm_skip")
             elif node_major:
                 bits = ptr(ymask) if (l == L - 1 and ymask.numel() > 0) else None  # [x_L > 0] as bits
                 check(lib.lg_gcn_bwd_nm_bits(ptr(nodetab_t), ptr(pairs_t), ptr(dy), ptr(xs[l + 1]), ptr(xs[l]),
@@ -1354,7 +1385,8 @@ def _trunk_layer_launches(lib, dy, xs, ymask, weights, sensor_slot, nodetab_t, p
 
 @gnn_trunk_backward.register_fake
 def _(grad_out, xs, ymask, h_s, proj_weight, weights, sensor_slot, sensor_idx, nonsensor_idx, slot_live, nodetab_t,
-      pairs_t, rowptr_t, col_t, w_t, p, node_major, x0bits, x0_bias, pos_slot_t, rowptr=None, col=None, *, bf16=False):
+      pairs_t, rowptr_t, col_t, w_t, p, node_major, x0bits, x0_bias, pos_slot_t, rowptr=None, col=None, *, bf16=False,
+      skip=False):
     D = proj_weight.shape[0]
     return (torch.empty_like(h_s), torch.empty_like(proj_weight), grad_out.new_empty(D),
             [torch.empty_like(t) for t in weights], [grad_out.new_empty(D) for _ in weights],
@@ -1365,6 +1397,7 @@ def _trunk_setup(ctx, inputs, keyword_only_inputs, output):
     (h_s, proj_weight, node_bias, weights, biases, sensor_slot, sensor_idx, nonsensor_idx, slot_live, _, _, rowptr, col,
      _, nodetab_t, pairs_t, rowptr_t, col_t, w_t, p, node_major, _, _, _, pos_slot_in, edge_w) = inputs
     bf16 = bool(keyword_only_inputs.get("bf16", False))
+    ctx.skip = bool(keyword_only_inputs.get("skip", False))
     # learned edge weights (requires_grad, not needs_input_grad: that tuple is flat over the tensor lists here)
     ctx.w_grad = edge_w is not None and edge_w.requires_grad
     # the dispatcher drops trailing arguments that equal their defaults before autograd sees
@@ -1399,7 +1432,7 @@ def _trunk_bwd(ctx, grads):
     dh_s, dWp, dbp, dWs, dbs, dw = torch.ops.leakgnn.gnn_trunk_backward(
         g, xs, ymask, h_s, proj_weight, weights, sensor_slot, sensor_idx, nonsensor_idx, live if ctx.has_live else None,
         nodetab_t, pairs_t, rowptr_t, col_t, w_t, ctx.p, ctx.node_major, x0bits if ctx.x0c else None,
-        node_bias if ctx.x0c else None, pos_slot_t if ctx.x0c else None, rowptr, col, bf16=ctx.bf16)
+        node_bias if ctx.x0c else None, pos_slot_t if ctx.x0c else None, rowptr, col, bf16=ctx.bf16, skip=ctx.skip)
     return ((dh_s, dWp, dbp, dWs, dbs) + (None,) * 20 + (dw if ctx.w_grad else None,))[:ctx.n_in]
 
 

@@ -52,7 +52,7 @@ from .loss import check_loss_args, loss_from_args
 from .optim import ClipAdamW
 from .predictor import NormalPredictorGRU, NormalPredictorTCN
 from .train_predictor import make_loader, pick_device, set_seed
-from .utils import build_residual_sequence_from_segment, now
+from .utils import build_residual_sequence_from_segment, now, sensor_reach
 from .window_evaluator import DetectorEvaluator
 
 
@@ -214,6 +214,11 @@ def main(argv=None, *, parse_only: bool = False):
                          "none = the unweighted graph")
     ap.add_argument("--learn_edge_weight", action="store_true",
                     help="learn the link weights (a parameter edge_log_weight, starting from --edge_weight, or from 1)")
+    ap.add_argument("--gnn_layers", type=int, default=2,
+                    help="GCN layers of the trunk; a node sees only the sensors within this many hops "
+                         "(utils.sensor_reach, printed at start-up)")
+    ap.add_argument("--skip", type=str, default="none", choices=["none", "residual"],
+                    help="residual: every GCN layer is x = x + dropout(relu(conv(x))), for trunks deeper than two layers")
     ap.add_argument("--label_smoothing", type=float, default=0.0,
                     help="label smoothing eps in [0, 1) of the training loss (0: none)")
     ap.add_argument("--smooth_sigma_m", type=float, default=0.0,
@@ -296,6 +301,10 @@ def main(argv=None, *, parse_only: bool = False):
 
     detector = detector_from_args(args.inp_path, sensor_ids, pipe_ids_in_order, vars(args), cls=LeakDetector,
                                   mlp_dtype=args.dtype).to(device)
+    out_n, out_p = sensor_reach(detector.edge_index_single, len(detector.node_names), detector.sensor_node_idx,
+                                detector.pipe_ends, args.gnn_layers)
+    print(f"{now()} [detector] gnn_layers={args.gnn_layers} skip={args.skip}: {out_n}/{len(detector.node_names)} nodes "
+          f"and {out_p}/{detector.pipe_ends.size(0)} pipes (both ends) out of reach of every sensor")
     clip = args.grad_clip if args.grad_clip and args.grad_clip > 0 else None
     fused_step = device.type == "cuda"  # clip_grad_norm_ + AdamW.step as one fused op pair
     if fused_step:

@@ -182,6 +182,36 @@ def link_edge_weights(inp_path: str | Path, include_links: Sequence[str] = ("PIP
     return torch.from_numpy((w / w.mean()).astype(np.float32))
 
 
+def sensor_reach(edge_index: Any, num_nodes: int, sensor_idx: Any, pipe_ends: Any, layers: int) -> Tuple[int, int]:
+    """(nodes_out_of_reach, pipes_out_of_reach) of a `layers`-layer GCN trunk: non-sensor nodes
+    start as dropout(relu(b)), so a node's features depend on the input only through the sensors
+    within `layers` hops of it.  Counts the nodes farther than that from every sensor and the
+    pipes (rows of pipe_ends, (P, 2) node indices) with BOTH ends among them, whose logit cannot
+    depend on the input.  edge_index (2, E) is taken as undirected.  Host only: one breadth-first
+    search from all sensors at once."""
+    ei = np.asarray(edge_index.cpu() if torch.is_tensor(edge_index) else edge_index, dtype=np.int64).reshape(2, -1)
+    adj: List[List[int]] = [[] for _ in range(num_nodes)]
+    for a, b in zip(ei[0].tolist(), ei[1].tolist()):
+        adj[a].append(b)
+        adj[b].append(a)
+    dist = np.full(num_nodes, -1, dtype=np.int64)
+    frontier = sorted({int(s) for s in np.asarray(sensor_idx.cpu() if torch.is_tensor(sensor_idx) else sensor_idx).reshape(-1)})
+    dist[frontier] = 0
+    d = 0
+    while frontier and d < int(layers):
+        d += 1
+        nxt = []
+        for u in frontier:
+            for v in adj[u]:
+                if dist[v] < 0:
+                    dist[v] = d
+                    nxt.append(v)
+        frontier = nxt
+    out = dist < 0
+    ends = np.asarray(pipe_ends.cpu() if torch.is_tensor(pipe_ends) else pipe_ends, dtype=np.int64).reshape(-1, 2)
+    return int(out.sum()), int((out[ends[:, 0]] & out[ends[:, 1]]).sum())
+
+
 # LEAKGNN_RESIDUAL=stock keeps the per-window module calls (for A/B timing).
 RESIDUAL_FAST_PATH = os.environ.get("LEAKGNN_RESIDUAL", "fast") != "stock"
 

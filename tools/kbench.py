@@ -303,7 +303,10 @@ def main():
     ap.add_argument("--probe", action="store_true", help="product-speed start/end timeline of each --nmlab train "
                                                           "launch of k_gcn_fwd_pc (LEAKGNN_LIB=lib/probe/libleakgnn.so, "
                                                           "built by `make lab LABNAME=probe LABDEF=-DLG_PC_PROBE`)")
-    ap.add_argument("--rounds", type=int, default=7, help="gru_stack leg: rounds of alternating windows")
+    ap.add_argument("--skip", action="store_true",
+                    help="time lg_gcn_fwd_nm_skip / lg_gcn_bwd_nm_skip against the plain bits forms (train mode, "
+                         "alternating over --rounds rounds; combine with --which '' to time nothing else)")
+    ap.add_argument("--rounds", type=int, default=7, help="gru_stack and --skip legs: rounds of alternating windows")
     ap.add_argument("--window-ms", type=float, default=250.0, help="gru_stack leg: device time per timed window")
     args = ap.parse_args()
     global GRAPH
@@ -410,6 +413,31 @@ def main():
         res[name] = {"us": t, "GBps": byts / t / 1e3}
         if args.stamps and hasattr(lib, "lg_lab_nm3_stamps"):
             res[name]["stamps"] = bwd_stamps_summary(lib, f)
+    if args.skip:  # the residual layer's kernels against the plain bits forms, alternating, --rounds rounds
+        dy = torch.randn_like(x)
+        dx = torch.empty_like(x)
+        dW, db = torch.empty(D, D, device=dev), torch.empty(D, device=dev)
+        ws = torch.empty(int(lib.lg_gcn_bwd_nm_workspace_bytes(D)), device=dev, dtype=torch.uint8)
+        bits = torch.empty(N * ((B + 15) // 16) * 64, device=dev, dtype=torch.int16)
+        tr = nat.LG_F_BIAS | nat.LG_F_RELU | nat.LG_F_DROPOUT
+        legs = {}
+        for nm_, fn in (("fwd_bits", lib.lg_gcn_fwd_nm_bits), ("fwd_skip", lib.lg_gcn_fwd_nm_skip)):
+            legs[nm_] = lambda fn=fn: check(fn(ptr(graph.nodetab), ptr(graph.pairs), ptr(x), ptr(W), ptr(bias), ptr(y),
+                                               B, N, D, E1, tr, 0.1, 123, 2, cs(), ptr(bits)), "skip fwd")
+        legs["fwd_bits"]()  # the mask bits the backward legs read
+        # an inner layer of the residual trunk (its own mask in, none out) in the step's transform
+        # (LG_F_BF16X3, ops.GCN_BWD_NM_EXTRA_FLAGS' default) and the kernel's own default (f16x2)
+        for tag, extra in (("x3", nat.LG_F_BF16X3), ("f16", 0)):
+            for nm_, fn in ((f"bwd_bits_{tag}", lib.lg_gcn_bwd_nm_bits), (f"bwd_skip_{tag}", lib.lg_gcn_bwd_nm_skip)):
+                legs[nm_] = lambda fn=fn, extra=extra: check(
+                    fn(ptr(graph.nodetab_t), ptr(graph.pairs_t), ptr(dy), None, ptr(x), ptr(W), ptr(dx), ptr(dW), ptr(db),
+                       None, None, B, N, D, nat.LG_F_MASK_IN | extra, 1.0 / 0.9, 1.0, ptr(ws), ws.numel(), cs(), ptr(bits)),
+                    "skip bwd")
+        runs = {k: [] for k in legs}
+        for _ in range(max(1, args.rounds)):
+            for k, f in legs.items():
+                runs[k].append(timeit(f, args.iters))
+        res["skip"] = {k: {"us_min": min(v), "us_max": max(v), "us": sorted(v)[len(v) // 2]} for k, v in runs.items()}
     if "node_init" in which:  # sensor projection + node init (x0 = B*N*D fp32 written, node-major)
         S5 = 29
         slot = torch.full((N,), -1, dtype=torch.int32, device=dev)
