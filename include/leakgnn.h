@@ -620,6 +620,41 @@ int lg_gcn_bwd_nm_skip(const int32_t* nodetab_t, const int32_t* pairs_t, const f
                        int flags, float scale_in, float scale_out, void* workspace, int64_t ws_bytes, lg_stream_t stream,
                        const uint16_t* ymask);
 
+/* LayerNorm over the feature axis, for the pre-norm residual trunk (added to ABI 26 without a
+ * bump: additions only):  xn_l = LN_l(x_l),  f_l = dropout(relu(Ahat xn_l W_l^T + b_l)),
+ * x_{l+1} = x_l + f_l.  The branch runs on lg_gcn_fwd_nm_bits / lg_gcn_bwd_nm_bits unchanged (their
+ * input may be signed); the add of the skip and the norm in front of the next branch are one
+ * launch here.  Rows are D contiguous floats (rows = N * B in either layout), D in {32, 64}
+ * (LG_EUNSUPPORTED otherwise), rows < 2^31.  wave64, one row per D/4 lanes, 16-byte loads and
+ * stores, no atomics; every result is bit-reproducible from run to run.
+ * lg_add_layernorm_fwd:
+ *   xsum = x + f                       one fp32 add per element; f and xsum both NULL: xsum is x
+ *                                      (the entry norm of x_0); one without the other: LG_EINVAL
+ *   mean = sum(xsum) / D,  var = sum((xsum - mean)^2) / D      two passes over the row in
+ *                                      registers, never E[x^2] - mean^2 (the stream grows with depth)
+ *   rstd = 1 / sqrt(var + eps)
+ *   xn   = (xsum - mean) * rstd * gamma + beta
+ *   stats [rows][2] = (mean, rstd), or NULL (inference).  x, xn, gamma, beta NULL, rows < 0 or
+ *   eps < 0: LG_EINVAL.  No output may alias an input.
+ * lg_layernorm_bwd: x is the forward's xsum, stats its (mean, rstd).  With xhat = (x - mean) * rstd,
+ *   g = dxn * gamma:
+ *   dx     = rstd * (g - mean(g) - xhat * mean(g * xhat))
+ *   dx     = dx + carry                when carry is non-NULL: one fp32 add (the gradient that
+ *                                      reaches x_l past the norm, through the skip)
+ *   dx_out = LG_F_MASK_OUT ? dx * scale_out * [x > 0] : dx     (the node init's ReLU / dropout
+ *                                      backward at the entry norm; the last arithmetic)
+ *   dgamma = sum_rows dxn * xhat,  dbeta = sum_rows dxn: per-workgroup partials in the workspace,
+ *   then the fixed-order slab reduction (inside an open reduce batch: recorded for its launch).
+ *   dx_out may alias no input.  flags other than LG_F_MASK_OUT: LG_EUNSUPPORTED.  workspace:
+ *   lg_layernorm_bwd_workspace_bytes(D) bytes, 16-byte aligned; NULL or fewer is LG_EINVAL, as is
+ *   a NULL dxn, x, stats, gamma, dx_out, dgamma or dbeta.  rows == 0 writes zeros to dgamma, dbeta. */
+int lg_add_layernorm_fwd(const float* x, const float* f, const float* gamma, const float* beta, float* xsum,
+                         float* xn, float* stats, int64_t rows, int64_t D, float eps, lg_stream_t stream);
+int64_t lg_layernorm_bwd_workspace_bytes(int64_t D);
+int lg_layernorm_bwd(const float* dxn, const float* x, const float* stats, const float* gamma, const float* carry,
+                     float* dx_out, float* dgamma, float* dbeta, int64_t rows, int64_t D, int flags, float scale_out,
+                     void* workspace, int64_t ws_bytes, lg_stream_t stream);
+
 /* Compressed layer-0 input (ABI 21).  The node init's non-sensor rows are dropout(relu(b)):
  * 632 of L-TOWN-A's 661 rows carry no information beyond their keep bits, yet materialising
  * x0 costs a 43 MB write and layer 0's forward and backward read it back (86 MB).

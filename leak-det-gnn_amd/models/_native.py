@@ -99,6 +99,10 @@ SIGNATURES = {
     # residual trunk layers (added to ABI 26 without a bump: additions only)
     "lg_gcn_fwd_nm_skip": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _f32, _u64, _u32, _p, _p]),
     "lg_gcn_bwd_nm_skip": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _f32, _f32, _p, _i64, _p, _p]),
+    # LayerNorm of the pre-norm residual trunk (csrc/norm.hip; added to ABI 26 without a bump)
+    "lg_add_layernorm_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _p]),
+    "lg_layernorm_bwd_workspace_bytes": (_i64, [_i64]),
+    "lg_layernorm_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _f32, _p, _i64, _p]),
     "lg_gcn_bwd_nm_workspace_bytes": (_i64, [_i64]),
     "lg_gcn_bwd_nm": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _f32, _f32, _p, _i64, _p]),
     "lg_edge_head_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i32, _f32,

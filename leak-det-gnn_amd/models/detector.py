@@ -42,6 +42,13 @@ node sees only sensors within gnn_layers hops: utils.sensor_reach).  The skip ru
 fp32-tier node-major kernels (lg_gcn_fwd_nm_skip / lg_gcn_bwd_nm_skip) at every batch size,
 through the unfused route: the encoder module, then leakgnn::gnn_trunk with x_0 materialised.
 skip="none" (the default) is the detector as before, bit for bit.
+
+Pre-norm trunk (LeakDetector(..., skip="residual", norm="layer"); not in the reference): a
+LayerNorm in front of every branch and one in front of the heads (self.norms, gnn_layers + 1
+stock nn.LayerNorm modules): xn_l = LN_l(x_l), x_{l+1} = x_l + dropout(relu(conv(xn_l))), the
+heads read xn_L.  The branch is the plain layer's kernel; the skip's add and the next norm are
+one launch (lg_add_layernorm_fwd, lg_layernorm_bwd: csrc/norm.hip) under leakgnn::gnn_trunk_norm.
+norm="none" (the default) is the detector as before: no `norms` attribute, no state-dict key.
 """
 from __future__ import annotations
 
@@ -173,14 +180,16 @@ class LeakDetector(nn.Module):
                  use_time: bool = True, include_links: Sequence[str] = ("PIPES", "PUMPS", "VALVES"),
                  mlp_dtype: str = "fp32", sensor_layers: int = 1, sensor_dropout: float = 0.0,
                  edge_weight: Optional[torch.Tensor] = None, learn_edge_weight: bool = False,
-                 skip: str = "none") -> None:
+                 skip: str = "none", norm: str = "none") -> None:
         """edge_weight: None, or a positive floating (n_links,) tensor, one weight per link in the
         order of the link table build_wdn_graph_from_inp walks (utils.link_edge_weights builds one
         from the .inp file); link j is the directed edges 2j and 2j + 1 of edge_index_single.
         learn_edge_weight: the link weights are learned, exp(edge_log_weight), starting from
         edge_weight (or 1).
         skip: "none", or "residual": every GCN layer x = x + dropout(relu(conv(x))).  An attribute
-        like mlp_dtype: no parameter, no state-dict entry."""
+        like mlp_dtype: no parameter, no state-dict entry.
+        norm: "none", or "layer" (needs skip="residual"): pre-norm, a LayerNorm in front of every
+        branch and of the heads; adds `norms` (gnn_layers + 1 nn.LayerNorm(node_hidden))."""
         super().__init__()
         if skip not in ("none", "residual"):
             raise ValueError(f"skip must be 'none' or 'residual', got {skip!r}")
@@ -188,6 +197,14 @@ class LeakDetector(nn.Module):
             raise NotImplementedError("skip='residual' needs mlp_dtype='fp32': the skip lives on the fp32-tier "
                                       "trunk kernels (lg_gcn_fwd_nm_skip / lg_gcn_bwd_nm_skip) only")
         self.skip = skip
+        if norm not in ("none", "layer"):
+            raise ValueError(f"norm must be 'none' or 'layer', got {norm!r}")
+        if norm == "layer" and skip != "residual":
+            raise ValueError("norm='layer' is the pre-norm residual block: it needs skip='residual'")
+        if norm == "layer" and mlp_dtype == "bf16":
+            raise NotImplementedError("norm='layer' needs mlp_dtype='fp32': the norm lives on the fp32-tier "
+                                      "trunk kernels (lg_add_layernorm_fwd / lg_layernorm_bwd) only")
+        self.norm = norm
         if mlp_dtype not in ("fp32", "bf16"):
             raise ValueError(f"mlp_dtype must be 'fp32' or 'bf16', got {mlp_dtype!r}")
         if learn_edge_weight and mlp_dtype == "bf16":
@@ -215,6 +232,8 @@ class LeakDetector(nn.Module):
         self.sensor_to_node = nn.Linear(sensor_hidden + 1, node_hidden)
         self.convs = nn.ModuleList(
             [GCNConv(node_hidden, node_hidden, add_self_loops=True, normalize=True) for _ in range(gnn_layers)])
+        if norm == "layer":
+            self.norms = nn.ModuleList(nn.LayerNorm(node_hidden) for _ in range(gnn_layers + 1))
         self.dropout = nn.Dropout(dropout)
         self.edge_head = EdgeHead(node_hidden, hidden_dim=128, dropout=dropout)
         self.noleak_head = NoLeakHead(node_hidden, hidden_dim=128, dropout=dropout)
@@ -392,9 +411,13 @@ class LeakDetector(nn.Module):
                 hit = ((src.data_ptr(), src._version), self._per_edge_weights(dev).repeat(B))
                 self._batched_weights[(B, dev)] = hit
             ew = hit[1]
-        for conv in self.convs:
-            br = F.dropout(F.relu(conv(x, ei) if ew is None else conv(x, ei, ew)), p, self.training)
+        ln = self.norm == "layer"
+        for l, conv in enumerate(self.convs):
+            xin = self.norms[l](x) if ln else x
+            br = F.dropout(F.relu(conv(xin, ei) if ew is None else conv(xin, ei, ew)), p, self.training)
             x = x + br if self.skip == "residual" else br
+        if ln:  # the heads read the normalised stream
+            x = self.norms[len(self.convs)](x)
         h_nodes = x.view(B, N, -1)
         ends = inc.ends.long()
         pipe_logits = self.edge_head(h_nodes[:, ends[:, 0]], h_nodes[:, ends[:, 1]])     # (B, P)
@@ -448,17 +471,31 @@ class LeakDetector(nn.Module):
                 self.capture["h_s"] = h_s
             # sensor_to_node (rows with a sensor: [h_s, 1] W^T + b; without: b) folded into node init
             mk = self._x0marks(g, slot) if (nm and self.compress_x0 and len(self.convs) > 1 and not skip) else None
-            out_t = torch.ops.leakgnn.gnn_trunk(
-                h_s, Wn, bn, [f(c.lin.weight) for c in self.convs], [f(c.bias) for c in self.convs], slot, sensor_idx,
-                nonsensor, slot_live, g.nodetab, g.pairs, g.rowptr, g.col, g.w, g.nodetab_t, g.pairs_t, g.rowptr_t,
-                g.col_t, g.w_t, float(self.dropout.p) if drop else 0.0, nm,
-                library.seed_tensor(residual.device) if drop else _NO_SEED,
-                mk.nodetab_s if mk is not None else None, mk.pairs_s if mk is not None else None,
-                mk.pos_slot_t if mk is not None else None, edge_w, bf16=bf16, **({"skip": True} if skip else {}))
-            xs = out_t[:-2]                     # [x_0 .. x_L] (then x_L's mask bits and x_0's, when compressed)
-            x0bits = out_t[-1]
-            ymask = out_t[-2]
-        h_nodes = xs[-1]                                                   # (N, B, D) node-major, else (B, N, D)
+            if self.norm == "layer":
+                nl = len(self.convs)
+                out_t = torch.ops.leakgnn.gnn_trunk_norm(
+                    h_s, Wn, bn, [f(c.lin.weight) for c in self.convs], [f(c.bias) for c in self.convs],
+                    [f(n.weight) for n in self.norms], [f(n.bias) for n in self.norms], slot, sensor_idx, nonsensor,
+                    slot_live, g.nodetab, g.pairs, g.rowptr, g.col, g.nodetab_t, g.pairs_t,
+                    float(self.dropout.p) if drop else 0.0, float(self.norms[0].eps),
+                    library.seed_tensor(residual.device) if drop else _NO_SEED, edge_w)
+                xs = list(out_t[1:nl + 2])          # the residual stream x_0 .. x_L
+                xns = list(out_t[nl + 2:2 * nl + 2]) + [out_t[0]]  # xn_0 .. xn_L; the heads read xn_L
+                ymask = out_t[-1]
+                x0bits = ymask[:0]
+            else:
+                out_t = torch.ops.leakgnn.gnn_trunk(
+                    h_s, Wn, bn, [f(c.lin.weight) for c in self.convs], [f(c.bias) for c in self.convs], slot, sensor_idx,
+                    nonsensor, slot_live, g.nodetab, g.pairs, g.rowptr, g.col, g.w, g.nodetab_t, g.pairs_t, g.rowptr_t,
+                    g.col_t, g.w_t, float(self.dropout.p) if drop else 0.0, nm,
+                    library.seed_tensor(residual.device) if drop else _NO_SEED,
+                    mk.nodetab_s if mk is not None else None, mk.pairs_s if mk is not None else None,
+                    mk.pos_slot_t if mk is not None else None, edge_w, bf16=bf16, **({"skip": True} if skip else {}))
+                xs = out_t[:-2]                     # [x_0 .. x_L] (then x_L's mask bits and x_0's, when compressed)
+                x0bits = out_t[-1]
+                ymask = out_t[-2]
+        # (N, B, D) node-major, else (B, N, D); under norm="layer" the last norm's output
+        h_nodes = xns[-1] if self.norm == "layer" else xs[-1]
         if self.keep_boundary:
             self.boundary = h_nodes
         mlp = self.edge_head.mlp     # Linear(3D,128), ReLU, Dropout, Linear(128,1)
@@ -480,6 +517,8 @@ class LeakDetector(nn.Module):
             if skip:  # the branches' keep decisions [f > 0], which xs[l] > 0 no longer is
                 nl = len(self.convs)
                 self.capture["fmask"] = [_unpack_mask(w, N, B, D) for w in ymask.view(nl, -1)] if nl else []
+            if self.norm == "layer":  # the branches' inputs and the heads' (xs stays the residual stream)
+                self.capture["xns"] = xns
         return out[0]
 
 
@@ -506,16 +545,19 @@ def detector_from_args(inp_path: str | Path, sensor_ids: Sequence[str], pipe_ids
     or a checkpoint's ckpt["args"].  "edge_weight" in {none, ones, length, inv_length, conductance}
     (utils.link_edge_weights) and "learn_edge_weight"; a missing key is the unweighted detector.
     "gnn_layers" (default 2) and "skip" in {none, residual} (default none): a missing key is the
-    two-layer plain trunk, so checkpoints from before these flags load as before.
+    two-layer plain trunk, so checkpoints from before these flags load as before.  "norm" in {none,
+    layer} (default none) likewise.
     cls: the class to build (the caller's own LeakDetector name; default: this module's)."""
     args = args or {}
     mode = args.get("edge_weight") or "none"
     ew = link_edge_weights(inp_path, mode=mode) if mode != "none" else None
     skip = args.get("skip") or "none"
+    norm = args.get("norm") or "none"
     return (cls or LeakDetector)(inp_path, sensor_ids, pipe_ids_in_order, sensor_hidden=64, node_hidden=64,
                                  gnn_layers=int(args.get("gnn_layers") or 2), dropout=0.1, use_time=True,
                                  edge_weight=ew, learn_edge_weight=bool(args.get("learn_edge_weight", False)),
-                                 **({"skip": skip} if skip != "none" else {}), **kwargs)
+                                 **({"skip": skip} if skip != "none" else {}),
+                                 **({"norm": norm} if norm != "none" else {}), **kwargs)
 
 
 def detector_from_checkpoint(ckpt: dict, inp_path: str | Path, **kwargs) -> LeakDetector:

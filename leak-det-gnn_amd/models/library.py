@@ -1257,15 +1257,21 @@ def _trunk_backward_launches(lib, dy, xs, ymask, h_s, proj_weight, weights, sens
     dy = _trunk_layer_launches(lib, dy, xs, ymask, weights, sensor_slot, nodetab_t, pairs_t, rowptr_t, col_t, w_t,
                                node_major, bf16, scale, wss, dWs, dbs, dbias_ns, st, x0c, p, wgrad, skip)
     L = len(weights)
-    dev = dy.device
     if node_major:
         N, B, D = xs[-1].shape
     else:
         B, N, D = xs[0].shape
-    S, Ds = h_s.shape[1], h_s.shape[2]
     if L == 0:  # no layer-0 launch applied the node init's relu/dropout mask
         dy = dy * (xs[0] > 0) * scale
         dbias_ns = dy.index_select(0 if node_major else 1, nonsensor_idx).sum(dim=(0, 1))
+    return _sensor_proj_backward(lib, dy, h_s, proj_weight, sensor_idx, slot_live, dbias_ns, B, N, D, node_major, wss, st)
+
+
+def _sensor_proj_backward(lib, dy, h_s, proj_weight, sensor_idx, slot_live, dbias_ns, B, N, D, node_major, wss, st):
+    """(dh_s, dproj_weight, dnode_bias) from the node init's pre-activation gradient dy (ONE
+    lg_sensor_proj_bwd) and the non-sensor rows' bias sum dbias_ns.  The workspace joins wss."""
+    dev = dy.device
+    S, Ds = h_s.shape[1], h_s.shape[2]
     dh_s = torch.empty(B, S, Ds, device=dev, dtype=torch.float32)
     dWp = torch.empty(D, Ds + 1, device=dev, dtype=torch.float32)
     dbp = torch.empty(D, device=dev, dtype=torch.float32)
@@ -1437,6 +1443,210 @@ def _trunk_bwd(ctx, grads):
 
 
 gnn_trunk.register_autograd(_trunk_bwd, setup_context=_trunk_setup)
+
+
+# ============================================================================ gnn_trunk_norm
+# The pre-norm residual trunk (LeakDetector(skip="residual", norm="layer")): a LayerNorm in front
+# of every branch and one in front of the heads,
+#   xn_l = LN_l(x_l),  f_l = dropout(relu(Ahat xn_l W_l^T + b_l)),  x_{l+1} = x_l + f_l,  out = xn_L.
+# Node-major, fp32 tier, dense node init.  The branch is the plain layer's kernel on a signed input
+# (lg_gcn_fwd_nm_bits, every layer's [f > 0] bits kept); the skip's add and the next norm are one
+# launch (lg_add_layernorm_fwd).  An op pair of its own: gnn_trunk's return layout stays as it is.
+LN_EPS = 1e-5  # nn.LayerNorm's default
+
+
+def _ln_fwd(lib, x, f, gamma, beta, xsum, xn, stats, eps, st):
+    check(lib.lg_add_layernorm_fwd(ptr(x), ptr(f), ptr(gamma), ptr(beta), ptr(xsum), ptr(xn), ptr(stats),
+                                   x.numel() // x.shape[-1], x.shape[-1], eps, st), "lg_add_layernorm_fwd")
+
+
+@torch.library.custom_op(f"{NS}::gnn_trunk_norm", mutates_args=(), device_types="cuda")
+def gnn_trunk_norm(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List[Tensor], biases: List[Tensor],
+                   gammas: List[Tensor], betas: List[Tensor], sensor_slot: Tensor, sensor_idx: Tensor,
+                   nonsensor_idx: Tensor, slot_live: Optional[Tensor], nodetab: Tensor, pairs: Tensor, rowptr: Tensor,
+                   col: Tensor, nodetab_t: Tensor, pairs_t: Tensor, p: float, eps: float, seed: Tensor,
+                   edge_w: Optional[Tensor] = None) -> List[Tensor]:
+    """[xn_L, x_0 .. x_L, xn_0 .. xn_{L-1}, stats, ymask], all node-major (N, B, D).
+    xn_L (the heads' input) is the one differentiable output.  x_l: the residual stream; xn_l: the
+    branches' inputs; stats (L + 1, N * B, 2): every norm's (mean, rstd); ymask (L * nmask,) int16:
+    layer l's [f_l > 0] words at [l * nmask, (l + 1) * nmask) (gnn_trunk's layout under skip).
+    gammas, betas: the L + 1 norms' weight and bias.  The backward keeps x_l AND xn_l per layer,
+    two activations where the skip keeps one.  edge_w: gnn_trunk's autograd anchor."""
+    lib = load_library()
+    h_s, proj_weight, node_bias = _c(h_s), _c(proj_weight), _c(node_bias)
+    weights, biases = [_c(t) for t in weights], [_c(t) for t in biases]
+    gammas, betas = [_c(t) for t in gammas], [_c(t) for t in betas]
+    _req(h_s, proj_weight, node_bias, *weights, *biases, *gammas, *betas)
+    B, S, Ds = h_s.shape
+    D = proj_weight.shape[0]
+    _check_d(D)
+    L = len(weights)
+    if len(biases) != L or len(gammas) != L + 1 or len(betas) != L + 1:
+        raise ValueError(f"gnn_trunk_norm: {L} layers need {L} biases and {L + 1} norms, got {len(biases)}, "
+                         f"{len(gammas)} and {len(betas)}")
+    if any(tuple(t.shape) != (D,) for t in gammas + betas):
+        raise ValueError(f"gnn_trunk_norm: every norm's weight and bias must be ({D},)")
+    if tuple(proj_weight.shape) != (D, Ds + 1):
+        raise ValueError(f"proj_weight must be (D, Ds + 1) = ({D}, {Ds + 1}), got {tuple(proj_weight.shape)}")
+    N = sensor_slot.shape[0]
+    dev = h_s.device
+    drop = p > 0.0
+    seed_v, sbit = _seed_args(seed) if drop else (0, 0)
+    dflag = nat.LG_F_DROPOUT if drop else 0
+    st = stream_of(h_s)
+    nmask = N * ((B + 15) // 16) * 64
+    new = lambda: torch.empty((N, B, D), device=dev, dtype=torch.float32)  # noqa: E731
+    x0 = new()
+    with _timed("node_init", dev):
+        check(lib.lg_node_init_proj_fwd(ptr(sensor_slot), ptr(sensor_idx), ptr(h_s), ptr(proj_weight), ptr(node_bias),
+                                        ptr(x0), B, N, S, Ds, D, dflag | nat.LG_F_NODE_MAJOR, p, seed_v, 0 | sbit, st),
+              "lg_node_init_proj_fwd")
+    stats = torch.empty((L + 1, N * B, 2), device=dev, dtype=torch.float32)
+    ymask = torch.empty(nmask * L, device=dev, dtype=torch.int16)
+    xs, xns = [x0], [new()]
+    with _timed("layernorm_fwd", dev):
+        _ln_fwd(lib, x0, None, gammas[0], betas[0], None, xns[0], stats[0], eps, st)
+    flags = nat.LG_F_BIAS | nat.LG_F_RELU | dflag | (GCN_FWD_NM_EXTRA_FLAGS & nat.LG_F_BF16X3)
+    for l, (W, b) in enumerate(zip(weights, biases)):
+        f = new()
+        with _timed("gcn_fwd", dev):
+            check(lib.lg_gcn_fwd_nm_bits(ptr(nodetab), ptr(pairs), ptr(xns[l]), ptr(W), ptr(b), ptr(f), B, N, D,
+                                         col.numel(), flags, p, seed_v, (l + 1) | sbit, st,
+                                         ptr(ymask[l * nmask:(l + 1) * nmask])), "lg_gcn_fwd_nm_bits")
+        xs.append(new())
+        xns.append(new())
+        with _timed("layernorm_fwd", dev):
+            _ln_fwd(lib, xs[l], f, gammas[l + 1], betas[l + 1], xs[l + 1], xns[l + 1], stats[l + 1], eps, st)
+    return [xns[L]] + xs + xns[:L] + [stats, ymask]
+
+
+@gnn_trunk_norm.register_fake
+def _(h_s, proj_weight, node_bias, weights, biases, gammas, betas, sensor_slot, sensor_idx, nonsensor_idx, slot_live,
+      nodetab, pairs, rowptr, col, nodetab_t, pairs_t, p, eps, seed, edge_w=None):
+    B, D, N, L = h_s.shape[0], proj_weight.shape[0], sensor_slot.shape[0], len(weights)
+    nmask = N * ((B + 15) // 16) * 64
+    return ([h_s.new_empty((N, B, D)) for _ in range(2 * L + 2)] + [h_s.new_empty((L + 1, N * B, 2))]
+            + [h_s.new_empty((nmask * L,), dtype=torch.int16)])
+
+
+@torch.library.custom_op(f"{NS}::gnn_trunk_norm_backward", mutates_args=(), device_types="cuda")
+def gnn_trunk_norm_backward(grad_out: Tensor, xs: List[Tensor], xns: List[Tensor], stats: Tensor, ymask: Tensor,
+                            h_s: Tensor, proj_weight: Tensor, weights: List[Tensor], gammas: List[Tensor],
+                            sensor_slot: Tensor, sensor_idx: Tensor, nonsensor_idx: Tensor,
+                            slot_live: Optional[Tensor], nodetab_t: Tensor, pairs_t: Tensor, p: float,
+                            rowptr: Optional[Tensor] = None, col: Optional[Tensor] = None
+                            ) -> Tuple[Tensor, Tensor, Tensor, List[Tensor], List[Tensor], List[Tensor], List[Tensor],
+                                       Tensor]:
+    """(dh_s, dproj_weight, dnode_bias, [dW_l], [db_l], [dgamma_l], [dbeta_l], dw).  With s = 1/(1-p)
+    and a_l = dL/dx_l (which is also dL/df_{l-1}):
+      a_L   = LNbwd_L(grad_out)
+      dxn_l = (Ahat^T (a_{l+1} * s * [f_l > 0])) W_l, dW_l, db_l   lg_gcn_bwd_nm_bits, LG_F_MASK_IN on
+                                                                  the layer's words, input xn_l
+      a_l   = LNbwd_l(dxn_l) + a_{l+1}                             lg_layernorm_bwd with the carry
+    and the entry norm's call applies the node init's mask (LG_F_MASK_OUT: a_0 * s * [x_0 > 0]).
+    xs: x_0 .. x_L, xns: xn_0 .. xn_{L-1}.  rowptr, col (the forward CSR): the edge coefficients
+    learn; layer l's share is lg_sddmm_nm on (a_{l+1}, xn_l, the layer's words)."""
+    lib = load_library()
+    L = len(weights)
+    dev = grad_out.device
+    st = stream_of(grad_out)
+    N, B, D = xs[0].shape
+    rows = N * B
+    scale = 1.0 / (1.0 - p) if p > 0.0 else 1.0
+    nmask = ymask.numel() // L if L else 0
+    wgrad = _WGrad(rowptr, col) if rowptr is not None else None
+    lnb, gcb = int(lib.lg_layernorm_bwd_workspace_bytes(D)), int(lib.lg_gcn_bwd_nm_workspace_bytes(D))
+    wss: List[Tensor] = []  # every workspace lives until the reduce batch is flushed
+
+    def ws(nbytes):
+        wss.append(torch.empty(nbytes, device=dev, dtype=torch.uint8))
+        return wss[-1]
+
+    def ln_bwd(l, dxn, carry):
+        dx = torch.empty((N, B, D), device=dev, dtype=torch.float32)
+        dg, dbt = torch.empty(D, device=dev, dtype=torch.float32), torch.empty(D, device=dev, dtype=torch.float32)
+        w = ws(lnb)
+        with _timed("layernorm_bwd", dev):
+            check(lib.lg_layernorm_bwd(ptr(dxn), ptr(xs[l]), ptr(stats[l]), ptr(gammas[l]), ptr(carry), ptr(dx), ptr(dg),
+                                       ptr(dbt), rows, D, nat.LG_F_MASK_OUT if l == 0 else 0, scale, ptr(w), w.numel(),
+                                       st), "lg_layernorm_bwd")
+        dgs[l], dbts[l] = dg, dbt
+        return dx
+
+    dWs: List[Tensor] = [grad_out] * L
+    dbs: List[Tensor] = [grad_out] * L
+    dgs: List[Tensor] = [grad_out] * (L + 1)
+    dbts: List[Tensor] = [grad_out] * (L + 1)
+    with _reduce_batch(lib, st):
+        a = ln_bwd(L, grad_out.contiguous(), None)
+        for l in range(L - 1, -1, -1):
+            words = ymask[l * nmask:(l + 1) * nmask]
+            if wgrad is not None:
+                wgrad.add(sddmm_nm(wgrad.rowptr, wgrad.col, a, weights[l], xns[l], ymask=words, mask_in=True,
+                                   scale=scale))
+            dxn = torch.empty_like(a)
+            dW = torch.empty(D, D, device=dev, dtype=torch.float32)
+            db = torch.empty(D, device=dev, dtype=torch.float32)
+            w = ws(gcb)
+            with _timed("gcn_bwd" if l == L - 1 else f"gcn_bwd_l{l}", dev):
+                check(lib.lg_gcn_bwd_nm_bits(ptr(nodetab_t), ptr(pairs_t), ptr(a), None, ptr(xns[l]), ptr(weights[l]),
+                                             ptr(dxn), ptr(dW), ptr(db), None, None, B, N, D,
+                                             nat.LG_F_MASK_IN | GCN_BWD_NM_EXTRA_FLAGS, scale, 1.0, ptr(w), w.numel(),
+                                             st, ptr(words)), "lg_gcn_bwd_nm_bits")
+            dWs[l], dbs[l] = dW, db
+            a = ln_bwd(l, dxn, a)
+        # a: the node init's pre-activation gradient; its non-sensor rows' sum is the bias's share
+        dbias_ns = a.index_select(0, nonsensor_idx).sum(dim=(0, 1))
+        dh_s, dWp, dbp = _sensor_proj_backward(lib, a, h_s, proj_weight, sensor_idx, slot_live, dbias_ns, B, N, D,
+                                               True, wss, st)
+    return (dh_s, dWp, dbp, dWs, dbs, dgs, dbts,
+            wgrad.total(dev) if wgrad is not None else torch.empty(0, device=dev))
+
+
+@gnn_trunk_norm_backward.register_fake
+def _(grad_out, xs, xns, stats, ymask, h_s, proj_weight, weights, gammas, sensor_slot, sensor_idx, nonsensor_idx,
+      slot_live, nodetab_t, pairs_t, p, rowptr=None, col=None):
+    D = proj_weight.shape[0]
+    return (torch.empty_like(h_s), torch.empty_like(proj_weight), grad_out.new_empty(D),
+            [torch.empty_like(t) for t in weights], [grad_out.new_empty(D) for _ in weights],
+            [torch.empty_like(t) for t in gammas], [torch.empty_like(t) for t in gammas],
+            grad_out.new_empty(col.shape[0] if col is not None else 0))
+
+
+def _trunk_norm_setup(ctx, inputs, output):
+    (h_s, proj_weight, _, weights, _, gammas, _, sensor_slot, sensor_idx, nonsensor_idx, slot_live, _, _, rowptr, col,
+     nodetab_t, pairs_t, p, _, _, edge_w) = inputs
+    ctx.w_grad = edge_w is not None and edge_w.requires_grad
+    ctx.n_in = 21 if edge_w is not None else 20  # the dispatcher drops a trailing default (see _trunk_setup)
+    L = ctx.L = len(weights)
+    ctx.mark_non_differentiable(*output[1:])
+    ctx.set_materialize_grads(False)
+    ctx.p, ctx.has_live = p, slot_live is not None
+    ctx.save_for_backward(*output[1:], h_s, proj_weight, *weights, *gammas, sensor_slot, sensor_idx, nonsensor_idx,
+                          slot_live if slot_live is not None else sensor_slot, nodetab_t, pairs_t,
+                          *((rowptr, col) if ctx.w_grad else ()))
+    assert len(output) == 2 * L + 4
+
+
+def _trunk_norm_bwd(ctx, grads):
+    L = ctx.L
+    sv = ctx.saved_tensors
+    g = grads[0]
+    if g is None:
+        return (None,) * ctx.n_in
+    xs, xns, stats, ymask = list(sv[:L + 1]), list(sv[L + 1:2 * L + 1]), sv[2 * L + 1], sv[2 * L + 2]
+    k = 2 * L + 3
+    h_s, proj_weight = sv[k], sv[k + 1]
+    weights, gammas = list(sv[k + 2:k + 2 + L]), list(sv[k + 2 + L:k + 3 + 2 * L])
+    sensor_slot, sensor_idx, nonsensor_idx, live, nodetab_t, pairs_t = sv[k + 3 + 2 * L:k + 9 + 2 * L]
+    rowptr, col = sv[k + 9 + 2 * L:] if ctx.w_grad else (None, None)
+    dh_s, dWp, dbp, dWs, dbs, dgs, dbts, dw = torch.ops.leakgnn.gnn_trunk_norm_backward(
+        g, xs, xns, stats, ymask, h_s, proj_weight, weights, gammas, sensor_slot, sensor_idx, nonsensor_idx,
+        live if ctx.has_live else None, nodetab_t, pairs_t, ctx.p, rowptr, col)
+    return ((dh_s, dWp, dbp, dWs, dbs, dgs, dbts) + (None,) * 13 + (dw if ctx.w_grad else None,))[:ctx.n_in]
+
+
+gnn_trunk_norm.register_autograd(_trunk_norm_bwd, setup_context=_trunk_norm_setup)
 
 
 # ============================================================================ encoder_trunk

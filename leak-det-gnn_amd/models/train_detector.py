@@ -219,6 +219,9 @@ def main(argv=None, *, parse_only: bool = False):
                          "(utils.sensor_reach, printed at start-up)")
     ap.add_argument("--skip", type=str, default="none", choices=["none", "residual"],
                     help="residual: every GCN layer is x = x + dropout(relu(conv(x))), for trunks deeper than two layers")
+    ap.add_argument("--norm", type=str, default="none", choices=["none", "layer"],
+                    help="layer: pre-norm, a LayerNorm in front of every GCN branch and of the heads "
+                         "(needs --skip residual); for trunks of 8 to 12 layers")
     ap.add_argument("--label_smoothing", type=float, default=0.0,
                     help="label smoothing eps in [0, 1) of the training loss (0: none)")
     ap.add_argument("--smooth_sigma_m", type=float, default=0.0,
@@ -303,7 +306,7 @@ def main(argv=None, *, parse_only: bool = False):
                                   mlp_dtype=args.dtype).to(device)
     out_n, out_p = sensor_reach(detector.edge_index_single, len(detector.node_names), detector.sensor_node_idx,
                                 detector.pipe_ends, args.gnn_layers)
-    print(f"{now()} [detector] gnn_layers={args.gnn_layers} skip={args.skip}: {out_n}/{len(detector.node_names)} nodes "
+    print(f"{now()} [detector] gnn_layers={args.gnn_layers} skip={args.skip} norm={args.norm}: {out_n}/{len(detector.node_names)} nodes "
           f"and {out_p}/{detector.pipe_ends.size(0)} pipes (both ends) out of reach of every sensor")
     clip = args.grad_clip if args.grad_clip and args.grad_clip > 0 else None
     fused_step = device.type == "cuda"  # clip_grad_norm_ + AdamW.step as one fused op pair

@@ -306,7 +306,11 @@ def main():
     ap.add_argument("--skip", action="store_true",
                     help="time lg_gcn_fwd_nm_skip / lg_gcn_bwd_nm_skip against the plain bits forms (train mode, "
                          "alternating over --rounds rounds; combine with --which '' to time nothing else)")
-    ap.add_argument("--rounds", type=int, default=7, help="gru_stack and --skip legs: rounds of alternating windows")
+    ap.add_argument("--norm", action="store_true",
+                    help="time lg_add_layernorm_fwd / lg_layernorm_bwd against the torch composition on the same "
+                         "tensors (x + f, F.layer_norm; its backward, then + carry), alternating over --rounds rounds; "
+                         "combine with --which '' to time nothing else")
+    ap.add_argument("--rounds", type=int, default=7, help="gru_stack, --skip and --norm legs: rounds of alternating windows")
     ap.add_argument("--window-ms", type=float, default=250.0, help="gru_stack leg: device time per timed window")
     args = ap.parse_args()
     global GRAPH
@@ -438,6 +442,44 @@ def main():
             for k, f in legs.items():
                 runs[k].append(timeit(f, args.iters))
         res["skip"] = {k: {"us_min": min(v), "us_max": max(v), "us": sorted(v)[len(v) // 2]} for k, v in runs.items()}
+    if args.norm:  # the pre-norm trunk's row kernels against torch on the same tensors, alternating
+        rows = N * B
+        xr, fr = torch.randn(rows, D, device=dev), torch.relu(torch.randn(rows, D, device=dev))
+        gam, bet = torch.randn(D, device=dev), torch.randn(D, device=dev)
+        xsum, xn, stats = torch.empty_like(xr), torch.empty_like(xr), torch.empty(rows, 2, device=dev)
+        dxn, carry, dxo = torch.randn_like(xr), torch.randn_like(xr), torch.empty_like(xr)
+        dg, dbt = torch.empty(D, device=dev), torch.empty(D, device=dev)
+        ws = torch.empty(int(lib.lg_layernorm_bwd_workspace_bytes(D)), device=dev, dtype=torch.uint8)
+        eps = 1e-5
+
+        def hip_fwd():
+            check(lib.lg_add_layernorm_fwd(ptr(xr), ptr(fr), ptr(gam), ptr(bet), ptr(xsum), ptr(xn), ptr(stats), rows, D,
+                                           eps, cs()), "norm fwd")
+
+        def hip_bwd():
+            check(lib.lg_layernorm_bwd(ptr(dxn), ptr(xsum), ptr(stats), ptr(gam), ptr(carry), ptr(dxo), ptr(dg), ptr(dbt),
+                                       rows, D, 0, 1.0, ptr(ws), ws.numel(), cs()), "norm bwd")
+
+        hip_fwd()
+        torch.cuda.synchronize()
+        mean, rstd = stats[:, :1].contiguous(), stats[:, 1:].contiguous()
+
+        def torch_fwd():
+            return torch.nn.functional.layer_norm(xr + fr, (D,), gam, bet, eps)
+
+        def torch_bwd():  # what autograd runs for F.layer_norm's backward, then the skip's add
+            dx, dgm, dbe = torch.ops.aten.native_layer_norm_backward(dxn, xsum, [D], mean, rstd, gam, bet,
+                                                                     [True, True, True])
+            return dx + carry, dgm, dbe
+
+        legs = {"fwd_hip": hip_fwd, "fwd_torch": torch_fwd, "bwd_hip": hip_bwd, "bwd_torch": torch_bwd}
+        runs = {k: [] for k in legs}
+        for _ in range(max(1, args.rounds)):
+            for k, fn in legs.items():
+                runs[k].append(timeit(fn, args.iters))
+        byts = 4 * rows * D * 4  # four activation-sized passes each way (the torch route moves at least five)
+        res["norm"] = {k: {"us_min": min(v), "us_max": max(v), "us": sorted(v)[len(v) // 2],
+                           "GBps_4pass": byts / sorted(v)[len(v) // 2] / 1e3} for k, v in runs.items()}
     if "node_init" in which:  # sensor projection + node init (x0 = B*N*D fp32 written, node-major)
         S5 = 29
         slot = torch.full((N,), -1, dtype=torch.int32, device=dev)
