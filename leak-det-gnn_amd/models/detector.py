@@ -455,14 +455,11 @@ class LeakDetector(nn.Module):
             cw, cb = [f(c.lin.weight) for c in self.convs], [f(c.bias) for c in self.convs]
             save = torch.is_grad_enabled() and (edge_w is not None or any(t.requires_grad for t in gw + [Wn, bn] + cw + cb))
             tf = f(tfeat).contiguous() if enc.use_time else None
-            out_t = torch.ops.leakgnn.encoder_trunk(
+            trunk = library.trunk_fields("encoder_trunk", torch.ops.leakgnn.encoder_trunk(
                 f(residual), tf, *gw, Wn, bn, cw, cb, slot, sensor_idx, slot_live, g.nodetab, g.pairs, g.nodetab_t,
                 g.pairs_t, mk.nodetab_s, mk.pairs_s, mk.pos_slot_t, float(self.dropout.p) if drop else 0.0,
                 library.seed_tensor(residual.device) if drop else _NO_SEED, save, edge_w,
-                g.rowptr if edge_w is not None else None, g.col if edge_w is not None else None, bf16=bf16)
-            nl = len(self.convs)
-            xs = [out_t[nl + 1]] + list(out_t[:nl])  # [x_0 (its sensor rows), x_1 .. x_L]
-            x0bits = out_t[nl + 2]
+                g.rowptr if edge_w is not None else None, g.col if edge_w is not None else None, bf16=bf16))
         else:
             h_s = self.sensor_encoder(residual, tfeat)                        # (B, S, Ds)
             if self.capture is not None and torch.is_grad_enabled():
@@ -472,30 +469,24 @@ class LeakDetector(nn.Module):
             # sensor_to_node (rows with a sensor: [h_s, 1] W^T + b; without: b) folded into node init
             mk = self._x0marks(g, slot) if (nm and self.compress_x0 and len(self.convs) > 1 and not skip) else None
             if self.norm == "layer":
-                nl = len(self.convs)
-                out_t = torch.ops.leakgnn.gnn_trunk_norm(
+                trunk = library.trunk_fields("gnn_trunk_norm", torch.ops.leakgnn.gnn_trunk_norm(
                     h_s, Wn, bn, [f(c.lin.weight) for c in self.convs], [f(c.bias) for c in self.convs],
                     [f(n.weight) for n in self.norms], [f(n.bias) for n in self.norms], slot, sensor_idx, nonsensor,
                     slot_live, g.nodetab, g.pairs, g.rowptr, g.col, g.nodetab_t, g.pairs_t,
                     float(self.dropout.p) if drop else 0.0, float(self.norms[0].eps),
-                    library.seed_tensor(residual.device) if drop else _NO_SEED, edge_w)
-                xs = list(out_t[1:nl + 2])          # the residual stream x_0 .. x_L
-                xns = list(out_t[nl + 2:2 * nl + 2]) + [out_t[0]]  # xn_0 .. xn_L; the heads read xn_L
-                ymask = out_t[-1]
-                x0bits = ymask[:0]
+                    library.seed_tensor(residual.device) if drop else _NO_SEED, edge_w))
             else:
-                out_t = torch.ops.leakgnn.gnn_trunk(
+                trunk = library.trunk_fields("gnn_trunk", torch.ops.leakgnn.gnn_trunk(
                     h_s, Wn, bn, [f(c.lin.weight) for c in self.convs], [f(c.bias) for c in self.convs], slot, sensor_idx,
                     nonsensor, slot_live, g.nodetab, g.pairs, g.rowptr, g.col, g.w, g.nodetab_t, g.pairs_t, g.rowptr_t,
                     g.col_t, g.w_t, float(self.dropout.p) if drop else 0.0, nm,
                     library.seed_tensor(residual.device) if drop else _NO_SEED,
                     mk.nodetab_s if mk is not None else None, mk.pairs_s if mk is not None else None,
-                    mk.pos_slot_t if mk is not None else None, edge_w, bf16=bf16, **({"skip": True} if skip else {}))
-                xs = out_t[:-2]                     # [x_0 .. x_L] (then x_L's mask bits and x_0's, when compressed)
-                x0bits = out_t[-1]
-                ymask = out_t[-2]
+                    mk.pos_slot_t if mk is not None else None, edge_w, bf16=bf16, **({"skip": True} if skip else {})))
+        # xs: x_0 (its sensor rows while x0bits is non-empty) .. x_L; xns: under norm="layer" xn_0 .. xn_L
+        xs, xns, ymask, x0bits = trunk.xs, trunk.xns, trunk.ymask, trunk.x0bits
         # (N, B, D) node-major, else (B, N, D); under norm="layer" the last norm's output
-        h_nodes = xns[-1] if self.norm == "layer" else xs[-1]
+        h_nodes = trunk.h
         if self.keep_boundary:
             self.boundary = h_nodes
         mlp = self.edge_head.mlp     # Linear(3D,128), ReLU, Dropout, Linear(128,1)
@@ -511,7 +502,7 @@ class LeakDetector(nn.Module):
         out = torch.ops.leakgnn.detector_heads(h_nodes, *hw, inc.ends, inc.rowptr, inc.item, pe, pn, nm, keep, seed,
                                                sched, sched_hdr, bf16=bf16)
         if self.capture is not None:
-            if x0bits.numel() > 0:  # x_0 compressed: materialise it for the diagnostics
+            if x0bits is not None and x0bits.numel() > 0:  # x_0 compressed: materialise it for the diagnostics
                 xs = [library.expand_x0(xs[0], x0bits, slot, bn, N, float(self.dropout.p) if drop else 0.0)] + xs[1:]
             self.capture.update(xs=xs, node_major=nm, edge_hidden=out[1], noleak_hidden=out[3])
             if skip:  # the branches' keep decisions [f > 0], which xs[l] > 0 no longer is
@@ -529,7 +520,8 @@ def _unpack_mask(words: torch.Tensor, N: int, B: int, D: int) -> torch.Tensor:
     """The mask words of lg_gcn_fwd_nm_bits / _skip (include/leakgnn.h) as a bool (N, B, D) tensor:
     per node and 16-window tile 64 lanes, bit 4k + i of lane l = row 16g + (64 / (D/4)) k + l // (D/4),
     channel 4 (l % (D/4)) + i.  Diagnostics only (LeakDetector.capture)."""
-    T, lpr = (B + 15) // 16, D // 4
+    assert words.numel() == library.mask_words(N, B)
+    T, lpr = words.numel() // (64 * N), D // 4  # 16-window tiles per node
     rpp = 64 // lpr
     w = words.view(N, T, rpp, lpr).to(torch.int32) & 0xFFFF                     # [n][g][l // lpr][l % lpr]
     sh = (4 * torch.arange(16 // rpp, device=words.device).view(-1, 1) + torch.arange(4, device=words.device)).view(-1)

@@ -16,7 +16,9 @@ ordinary ops (fake / meta implementations give output shapes without running ker
   leakgnn::gru_stack           the same with num_layers > 1 (dense-input upper layers, inter-layer dropout)
   leakgnn::gru_predictor       NormalPredictorGRU's nn.GRU over a dense (B, L, I) input (MFMA layers at H = 128)
   leakgnn::tcn_predictor       NormalPredictorTCN's conv stack over the projected (B, L, 128) input, for training
-  leakgnn::gnn_trunk           node init + L x [GCNConv, ReLU, Dropout] (detector.py:178-201)
+  leakgnn::gnn_trunk           node init + L x [GCNConv, ReLU, Dropout] (detector.py:178-201); skip=True: identity skips
+  leakgnn::gnn_trunk_norm      the same with a LayerNorm before every residual branch and before the heads
+  leakgnn::encoder_trunk       gru_encoder + gnn_trunk as one op (node-major, compressed node init)
   leakgnn::detector_heads      pipe gather + EdgeHead + mean pool + NoLeakHead
                                (detector.py:76-102, 206-218)
   leakgnn::window_metrics      DetectorEvaluator.evaluate's per-batch tail (window_evaluator.py:227-483); no autograd
@@ -33,9 +35,12 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import dataclasses
+import functools
+import inspect
 
-from collections import OrderedDict
-from typing import List, Optional, Tuple
+from collections import OrderedDict, namedtuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -1078,6 +1083,306 @@ def expand_x0(xs0: Tensor, x0bits: Tensor, sensor_slot: Tensor, node_bias: Tenso
     return x0
 
 
+# ============================================================================ trunk ops: shared drivers
+# gnn_trunk, gnn_trunk_norm and encoder_trunk are one forward layer launch (_layer_forward) and one
+# backward layer launch (_layer_backward) over the C entry points, each op call described once by a
+# _Trunk.  What differs between the ops is passed in: the layer's input (x_l, its compressed form
+# under x0bits, the norm route's xn_l), the mask words it writes or reads, the forward flag rule
+# (branch) and the backward's masks.  Each op has one output layout (_*_layout: the real and the
+# fake body allocate from it, the autograd setup and trunk_fields read its positions), and the
+# autograd glue names what it saves (_save_named / _saved_named: the *_backward op's arguments by
+# keyword) and what it returns (_named_grads over the op's own parameter names).
+def mask_words(N: int, B: int) -> int:
+    """int16 words of one activation's [x > 0] bits (the layout of lg_gcn_fwd_nm_bits,
+    include/leakgnn.h): 64 lanes per node and 16-window tile."""
+    return N * ((B + 15) // 16) * 64
+
+
+def _layer_words(ymask: Tensor, l: int, L: int) -> Tensor:  # of a ymask with one mask per layer (skip, norm)
+    n = ymask.numel() // L
+    return ymask[l * n:(l + 1) * n]
+
+
+# One call of a trunk op (forward or backward): sizes, layout and tier, the dropout triple drop =
+# (dflag, seed_v, sbit), and the tables the call was given (None otherwise): the node tables, the
+# CSR triple where window-major needs it, their transposes in a backward, the sensor marks.
+_Trunk = dataclasses.make_dataclass("_Trunk", (
+    ["lib", "st", "dev", "B", "N", "S", "D", "L", "p", "scale", "drop"]
+    + [("node_major", bool, True), ("bf16", bool, False), ("skip", bool, False), ("nnz", int, 0)]
+    + [(k, Optional[Tensor], None) for k in (
+        "nodetab", "pairs", "rowptr", "col", "w", "nodetab_t", "pairs_t", "rowptr_t", "col_t", "w_t",
+        "nodetab_s", "pairs_s", "pos_slot_t", "sensor_slot", "node_bias")]))
+
+
+def _trunk(lib, ref: Tensor, B: int, N: int, S: int, D: int, L: int, p: float, seed: Optional[Tensor] = None, **kw):
+    """The _Trunk of a call on ref's device and stream.  seed: a forward's (a backward draws nothing)."""
+    drop = p > 0.0
+    seed_v, sbit = _seed_args(seed) if (drop and seed is not None) else (0, 0)
+    return _Trunk(lib=lib, st=stream_of(ref), dev=ref.device, B=B, N=N, S=S, D=D, L=L, p=p,
+                  scale=1.0 / (1.0 - p) if drop else 1.0, drop=(nat.LG_F_DROPOUT if drop else 0, seed_v, sbit), **kw)
+
+
+def _layer_forward(t: _Trunk, l: int, x: Tensor, W: Tensor, b: Tensor, y: Tensor, words: Optional[Tensor] = None, *,
+                   x0bits: Optional[Tensor] = None, branch: bool = False) -> None:
+    """y = dropout(relu(Ahat x W^T + b)) of layer l (salt l + 1), [y > 0] into `words` where given.
+    x0bits: x is the compressed node init's sensor rows (S, B, D), read through the marked table
+    (lg_gcn_fwd_nm_x0).  branch: the layer is a residual branch, lg_gcn_fwd_nm_skip (y = x + f,
+    t.skip) or the norm route's lg_gcn_fwd_nm_bits on xn_l; otherwise node-major
+    lg_gcn_fwd_nm_bits, window-major lg_gcn_fwd."""
+    lib, (dflag, seed_v, sbit) = t.lib, t.drop
+    flags = nat.LG_F_BIAS | nat.LG_F_RELU | dflag | (nat.LG_F_BF16 if t.bf16 else 0)
+    salt = (l + 1) | sbit
+    with _timed("gcn_fwd_l0" if x0bits is not None else "gcn_fwd", t.dev):
+        if x0bits is not None:
+            # the x0 kernel takes the trunk-forward flags alone (it has no dense-layer variants)
+            check(lib.lg_gcn_fwd_nm_x0(ptr(t.nodetab_s), ptr(t.pairs_s), ptr(x), ptr(x0bits), ptr(t.node_bias), ptr(W),
+                                       ptr(b), ptr(y), t.B, t.N, t.S, t.D, flags | GCN_FWD_NM_EXTRA_FLAGS, t.p, seed_v,
+                                       salt, t.st), "lg_gcn_fwd_nm_x0")
+        elif t.node_major:
+            if branch:  # its input is signed (the stream, or its norm): only the split-bf16 product applies
+                flags |= GCN_FWD_NM_EXTRA_FLAGS & nat.LG_F_BF16X3
+            else:       # the dense layers' own flags belong to the fp32 tier (bf16: one product, LG_F_BF16)
+                flags |= GCN_FWD_NM_EXTRA_FLAGS | (GCN_FWD_DENSE_EXTRA_FLAGS if not t.bf16 else 0)
+            fn, name = ((lib.lg_gcn_fwd_nm_skip, "lg_gcn_fwd_nm_skip") if t.skip else
+                        (lib.lg_gcn_fwd_nm_bits, "lg_gcn_fwd_nm_bits"))
+            check(fn(ptr(t.nodetab), ptr(t.pairs), ptr(x), ptr(W), ptr(b), ptr(y), t.B, t.N, t.D, t.nnz, flags, t.p,
+                     seed_v, salt, t.st, ptr(words)), name)
+        else:
+            check(lib.lg_gcn_fwd(ptr(t.rowptr), ptr(t.col), ptr(t.w), ptr(x), ptr(W), ptr(b), ptr(y), t.B, t.N, t.D,
+                                 t.nnz, flags, t.p, seed_v, salt, t.st), "lg_gcn_fwd")
+
+
+class _WGrad:
+    """dL/dw of the trunk's layers, collected by _layer_backward when the edge coefficients
+    learn (rowptr, col given: the forward CSR): G = sum over the layers of _layer_dw, added in the
+    order the backward visits them (last layer first), over the CSR's slots.  Otherwise empty."""
+
+    def __init__(self, rowptr: Optional[Tensor], col: Optional[Tensor]):
+        self.rowptr, self.col, self.G, self.on = rowptr, col, None, rowptr is not None
+
+    def add(self, G: Tensor) -> None:
+        self.G = G if self.G is None else self.G + G
+
+    def total(self, dev) -> Tensor:
+        return self.G if self.G is not None else torch.zeros(self.col.numel() if self.on else 0, device=dev)
+
+
+def _layer_dw(t: _Trunk, dy: Tensor, x: Tensor, y: Optional[Tensor], W: Tensor, words: Optional[Tensor],
+              mask_in: bool, x0bits: Optional[Tensor], rowptr: Tensor, col: Tensor) -> Tensor:
+    """One layer's share of dL/dw: G[k] = sum_b (dz W)[n, b] . x[col k, b] for every slot k of row n,
+    with dz = dy * scale * [f > 0] under mask_in (the last plain layer, every skip / norm branch:
+    the mask from the layer's bit words, else from its output y) and dz = dy otherwise (that dy is
+    the layer above's dx, which that launch already masked: LG_F_MASK_OUT), exactly the dz of the
+    layer's own backward launch.  Node-major: lg_sddmm_nm; the compressed node init is
+    materialised for layer 0 (lg_node_init_expand; a compressed-x0 form of the kernel is left for
+    later).  Window-major: da on a library GEMM, then ONE lg_sddmm_cols over the [N][B * D]
+    transposes.  Deterministic."""
+    if t.node_major:
+        if x0bits is not None:
+            x = expand_x0(x, x0bits, t.sensor_slot, t.node_bias, t.N, t.p)
+        return sddmm_nm(rowptr, col, dy, W, x, y=y if (mask_in and words is None) else None, ymask=words,
+                        mask_in=mask_in, scale=t.scale)
+    B, N, D = dy.shape
+    dz = dy * (y > 0) * t.scale if mask_in else dy
+    with torch.autocast("cuda", enabled=False):
+        da = (dz.reshape(B * N, D) @ W).view(B, N, D)
+    return torch.ops.leakgnn.sddmm_cols(rowptr, col, da.transpose(0, 1).reshape(N, B * D),
+                                        x.transpose(0, 1).reshape(N, B * D))
+
+
+def _layer_backward(t: _Trunk, l: int, dy: Tensor, x: Tensor, y: Optional[Tensor], W: Tensor, words: Optional[Tensor],
+                    ws: Tensor, *, mask_in: bool, mask_out: bool, scale_out: float, dbias_ns: Optional[Tensor] = None,
+                    x0bits: Optional[Tensor] = None, wgrad: Optional[_WGrad] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """(dx, dW, db) of layer l from dy, ONE fused launch: dz = dy * scale * [f > 0] under mask_in
+    (from `words`, else from the layer's output y), dx masked by the input's own ReLU / dropout
+    under mask_out and scaled by scale_out.  x: the layer's input (x_l; the norm route's xn_l, no
+    ReLU output: scale_out 1.0, no mask_out; under x0bits the compressed node init's sensor rows).
+    dbias_ns (layer 0 in front of the node init): the launch also sums dx's non-sensor rows into it
+    and writes dx for the sensor rows only (all lg_sensor_proj_bwd reads).  t.skip: dx = dy + the
+    branch's (lg_gcn_bwd_nm_skip).  wgrad: the layer's dL/dw is added first (_layer_dw)."""
+    lib, B, N, D = t.lib, t.B, t.N, t.D
+    flags = ((nat.LG_F_MASK_IN if mask_in else 0) | (nat.LG_F_MASK_OUT if mask_out else 0)
+             | (nat.LG_F_BF16 if t.bf16 else 0) | (GCN_BWD_NM_EXTRA_FLAGS if t.node_major and not t.bf16 else 0)
+             | (nat.LG_F_DX_SENSOR_ROWS if dbias_ns is not None else 0))
+    slot_p, dbias_p = (ptr(t.sensor_slot), ptr(dbias_ns)) if dbias_ns is not None else (None, None)
+    dx = torch.empty_like(dy)
+    dW, db = torch.empty(D, D, device=t.dev, dtype=torch.float32), torch.empty(D, device=t.dev, dtype=torch.float32)
+    if wgrad is not None and wgrad.on:
+        wgrad.add(_layer_dw(t, dy, x, y, W, words, mask_in, x0bits, wgrad.rowptr, wgrad.col))
+    with _timed("gcn_bwd" if l == t.L - 1 else f"gcn_bwd_l{l}", t.dev):
+        if x0bits is not None:
+            check(lib.lg_gcn_bwd_nm_x0(ptr(t.nodetab_t), ptr(t.pairs_t), ptr(t.pos_slot_t), ptr(dy), ptr(x), ptr(x0bits),
+                                       ptr(t.node_bias), ptr(W), ptr(dx), ptr(dW), ptr(db), slot_p, dbias_p, B, N, t.S,
+                                       D, flags | t.drop[0], t.p, t.scale, ptr(ws), ws.numel(), t.st),
+                  "lg_gcn_bwd_nm_x0")
+        elif t.node_major:
+            fn, name = ((lib.lg_gcn_bwd_nm_skip, "lg_gcn_bwd_nm_skip") if t.skip else
+                        (lib.lg_gcn_bwd_nm_bits, "lg_gcn_bwd_nm_bits"))
+            check(fn(ptr(t.nodetab_t), ptr(t.pairs_t), ptr(dy), ptr(y), ptr(x), ptr(W), ptr(dx), ptr(dW), ptr(db), slot_p,
+                     dbias_p, B, N, D, flags, t.scale, scale_out, ptr(ws), ws.numel(), t.st, ptr(words)), name)
+        else:
+            check(lib.lg_gcn_bwd(ptr(t.rowptr_t), ptr(t.col_t), ptr(t.w_t), ptr(dy), ptr(y), ptr(x), ptr(W), ptr(dx),
+                                 ptr(dW), ptr(db), slot_p, dbias_p, B, N, D, t.col_t.numel(), flags, t.scale, scale_out,
+                                 ptr(ws), ws.numel(), t.st), "lg_gcn_bwd")
+    return dx, dW, db
+
+
+def _trunk_layer_launches(t: _Trunk, dy: Tensor, xs, ymask: Tensor, weights, x0bits: Optional[Tensor], wgrad: _WGrad):
+    """The GCN layers' backward of gnn_trunk and encoder_trunk, last first: (dx0, [dW_l], [db_l],
+    dbias_ns, workspaces).  dx0: the node init's pre-activation gradient (layer 0's dx: masked by
+    the node init's ReLU / dropout; under x0bits the sensor nodes' rows only); dbias_ns: its
+    non-sensor rows' sum.  Plain: the last layer masks its output ([x_L > 0], from ymask's bits
+    where the forward wrote them), every layer its input.  t.skip: x_{l+1} = x_l + f_l, so
+    dx_l = dx_{l+1} + (branch); every layer applies its own mask (LG_F_MASK_IN on its bit words)
+    and only layer 0 a LG_F_MASK_OUT, the node init's."""
+    L, D, lib = t.L, t.D, t.lib
+    wsb = lib.lg_gcn_bwd_nm_workspace_bytes(D) if t.node_major else lib.lg_gcn_bwd_workspace_bytes(D)
+    # one workspace per layer: the layers' slab reductions run together at the batch flush
+    wss = [torch.empty(int(wsb), device=t.dev, dtype=torch.uint8) for _ in range(L)]
+    dWs, dbs = [dy] * L, [dy] * L
+    dbias_ns = torch.empty(D, device=t.dev, dtype=torch.float32)
+    for l in range(L - 1, -1, -1):
+        last = l == L - 1
+        words = (_layer_words(ymask, l, L) if t.skip else  # else [x_L > 0] as bits
+                 ymask if (t.node_major and last and ymask.numel() > 0) else None)
+        dy, dWs[l], dbs[l] = _layer_backward(
+            t, l, dy, xs[l], None if t.skip else xs[l + 1], weights[l], words, wss[l], mask_in=last or t.skip,
+            mask_out=l == 0 or not t.skip, scale_out=t.scale, dbias_ns=dbias_ns if l == 0 else None,
+            x0bits=x0bits if l == 0 else None, wgrad=wgrad)  # dx: already masked by the previous op's relu/dropout
+    return dy, dWs, dbs, dbias_ns, wss
+
+
+def _sensor_proj_backward(t: _Trunk, dy, h_s, proj_weight, sensor_idx, slot_live, dbias_ns, wss):
+    """(dh_s, dproj_weight, dnode_bias) from the node init's pre-activation gradient dy (ONE
+    lg_sensor_proj_bwd) and the non-sensor rows' bias sum dbias_ns.  The workspace joins wss."""
+    lib, dev, B, D = t.lib, t.dev, t.B, t.D
+    S, Ds = h_s.shape[1], h_s.shape[2]
+    dh_s, dbp = torch.empty(B, S, Ds, device=dev, dtype=torch.float32), torch.empty(D, device=dev, dtype=torch.float32)
+    dWp = torch.empty(D, Ds + 1, device=dev, dtype=torch.float32)
+    wsp = torch.empty(int(lib.lg_sensor_proj_bwd_workspace_bytes(B, S, Ds, D)), device=dev, dtype=torch.uint8)
+    wss.append(wsp)  # held by the caller until the reduce batch is flushed
+    with _timed("linear_dw", dev):
+        check(lib.lg_sensor_proj_bwd(ptr(dy), ptr(sensor_idx), ptr(slot_live), ptr(h_s), ptr(proj_weight),
+                                     ptr(dbias_ns), ptr(dh_s), ptr(dWp), ptr(dbp), B, t.N, S, Ds, D,
+                                     nat.LG_F_NODE_MAJOR if t.node_major else 0, ptr(wsp), wsp.numel(), t.st),
+              "lg_sensor_proj_bwd")
+    return dh_s, dWp, dbp
+
+
+# ---------------------------------------------------------------------------- output layouts
+# An op's output list: (entries, pos), one (shape, dtype) per entry and the named positions, each an index, a
+# list of indices or None (the op has no such output).  Sizes default to 0: the positions need L alone.
+_F32, _I16 = torch.float32, torch.int16
+
+
+def _alloc(lay, like: Tensor) -> List[Tensor]:
+    return [like.new_empty(shape, dtype=dt) for shape, dt in lay[0]]  # (a fake tensor gives fake ones)
+
+
+def _gnn_trunk_layout(L, B=0, N=0, S=0, D=0, node_major=True, skip=False, x0c=False):
+    """[x_0, ..., x_L, ymask, x0bits]; x_L is the heads' input.  x0c: x_0 is its sensor rows."""
+    act = (N, B, D) if node_major else (B, N, D)
+    nmask = mask_words(N, B) if (node_major and L > 0) else 0
+    return ([((S, B, D) if x0c else act, _F32)] + [(act, _F32)] * L
+            + [((nmask * (L if skip else 1),), _I16), ((nmask if x0c else 0,), _I16)],
+            dict(xs=list(range(L + 1)), xns=None, ymask=L + 1, x0bits=L + 2, h=L))
+
+
+def _gnn_trunk_norm_layout(L, B=0, N=0, D=0):
+    """[xn_L, x_0 .. x_L, xn_0 .. xn_{L-1}, stats, ymask]; xn_L is the heads' input."""
+    return ([((N, B, D), _F32)] * (2 * L + 2) + [((L + 1, N * B, 2), _F32), ((mask_words(N, B) * L,), _I16)],
+            dict(xs=list(range(1, L + 2)), xns=list(range(L + 2, 2 * L + 2)) + [0], ymask=2 * L + 3, x0bits=None, h=0,
+                 stats=2 * L + 2))
+
+
+def _encoder_trunk_layout(L, B=0, N=0, S=0, D=0, Lw=0, H=0, save=False):
+    """[x_1, ..., x_L, ymask, xs0, x0bits, h_seq, gates]; x_L is the heads' input.  h_seq / gates: the
+    fused GRU pair's saved steps, in 16-sequence blocks (empty unless save)."""
+    nmask, rows = mask_words(N, B), _gru_ni_rows(B * S)
+    return ([((N, B, D), _F32)] * L + [((nmask,), _I16), ((S, B, D), _F32), ((nmask,), _I16),
+                                       ((Lw, rows, H) if save else (0,), _F32), ((Lw, rows, 4, H) if save else (0,), _F32)],
+            dict(xs=[L + 1] + list(range(L)), xns=None, ymask=L, x0bits=L + 2, h=L - 1, h_seq=L + 3, gates=L + 4))
+
+
+_LAYOUTS = {"gnn_trunk": (_gnn_trunk_layout, lambda n: n - 3),  # op -> (layout, L of an output count)
+            "gnn_trunk_norm": (_gnn_trunk_norm_layout, lambda n: (n - 4) // 2),
+            "encoder_trunk": (_encoder_trunk_layout, lambda n: n - 5)}
+
+
+# A trunk op's outputs by name: xs = x_0 .. x_L (x_0 its sensor rows where x0bits is non-empty), xns =
+# xn_0 .. xn_L (gnn_trunk_norm), the mask words, h = the heads' input; then the ops' own.  None: no such output.
+TrunkOut = namedtuple("TrunkOut", "xs xns ymask x0bits h stats h_seq gates", defaults=(None, None, None))
+
+
+def _positions(op: str, n_out: int) -> Dict[str, object]:  # (no cache: torch.compile traces through here)
+    layout, layers = _LAYOUTS[op]
+    return layout(layers(n_out))[1]
+
+
+def trunk_fields(op: str, out) -> TrunkOut:
+    """The flat output list of leakgnn::<op> (gnn_trunk, gnn_trunk_norm, encoder_trunk) by name."""
+    return TrunkOut(**{k: None if i is None else out[i] if isinstance(i, int) else [out[j] for j in i]
+                       for k, i in _positions(op, len(out)).items()})
+
+
+# ---------------------------------------------------------------------------- autograd glue
+def _save_named(ctx, **named) -> None:
+    """save_for_backward of a mapping name -> tensor, tensor list or None; names, list lengths and
+    the None entries are recorded on ctx (a missing optional tensor saves nothing)."""
+    runs = {k: [] if v is None else [v] if isinstance(v, Tensor) else list(v) for k, v in named.items()}
+    ctx.saved_spec = tuple((k, None if v is None else -1 if isinstance(v, Tensor) else len(runs[k]))
+                           for k, v in named.items())  # (name, None | -1: a tensor | list length)
+    ctx.save_for_backward(*(t for run in runs.values() for t in run))
+
+
+def _saved_named(ctx) -> Dict[str, object]:
+    """The mapping _save_named was given, from ctx.saved_tensors."""
+    spec = ctx.saved_spec
+    runs = _split(ctx.saved_tensors, *(0 if n is None else 1 if n < 0 else n for _, n in spec))
+    return {name: None if n is None else run[0] if n < 0 else run for (name, n), run in zip(spec, runs)}
+
+
+@functools.lru_cache(maxsize=None)
+def _positional(op) -> Tuple[Tuple[str, ...], tuple]:
+    """(names, defaults) of a custom op's positional parameters (autograd sees no keyword-only one)."""
+    ps = [q for q in inspect.signature(op._init_fn).parameters.values() if q.kind is not q.KEYWORD_ONLY]
+    return tuple(q.name for q in ps), tuple(q.default for q in ps)
+
+
+def _args_seen(op, inputs) -> int:
+    """How many of `inputs` autograd saw: the dispatcher drops trailing arguments that equal
+    their defaults before autograd sees them, and the backward returns one entry per argument
+    it saw."""
+    _, defaults = _positional(op)
+    n = len(inputs)
+    while n > 0 and defaults[n - 1] is not inspect.Parameter.empty and not isinstance(inputs[n - 1], Tensor) \
+            and inputs[n - 1] == defaults[n - 1]:
+        n -= 1
+    return n
+
+
+def _named_grads(op, n_seen: int, **grads) -> tuple:
+    """A backward's return tuple: grads[name] at each of op's first n_seen parameters, None elsewhere."""
+    names = _positional(op)[0]
+    unknown = sorted(set(grads) - set(names))
+    if unknown:
+        raise KeyError(f"{op._qualname}: no parameter named {unknown}")
+    return tuple(grads.get(name) for name in names[:n_seen])
+
+
+def _trunk_ctx(ctx, op, inputs, output) -> Tuple[Dict[str, object], TrunkOut]:
+    """The trunk ops' setup_context in common; returns (inputs by name, outputs by name).  Sets ctx.w_grad, ctx.n_in
+    and ctx.h: the position of the heads' input, the one differentiable output (the rest serve the backward)."""
+    a, name = dict(zip(_positional(op)[0], inputs)), op._qualname.split("::")[1]
+    # learned edge weights (requires_grad, not needs_input_grad: that tuple is flat over the tensor lists here)
+    ctx.w_grad = a["edge_w"] is not None and a["edge_w"].requires_grad
+    ctx.n_in = _args_seen(op, inputs)
+    ctx.h = _positions(name, len(output))["h"]
+    ctx.mark_non_differentiable(*(o for i, o in enumerate(output) if i != ctx.h))
+    ctx.set_materialize_grads(False)  # their gradients would be zero-filled (B, N, D) tensors
+    return a, trunk_fields(name, output)
+
+
 # ============================================================================ gnn_trunk
 def _compress_x0(nodetab_s: Optional[Tensor], node_major: bool, L: int) -> bool:
     """Whether gnn_trunk keeps x_0 compressed (sensor rows + [x_0 > 0] bits).  Needs a layer
@@ -1107,7 +1412,7 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
     proj buffer).  node_major: features [N][B][D] (lg_gcn_fwd_nm), else [B][N][D].  p:
     dropout prob (0 = eval).  Every activation is returned: the backward reads its
     ReLU/dropout masks back as [x > 0] and needs x_l for dW.  ymask (node-major only, int16
-    (N * ceil(B/16) * 64,), else empty): [x_L > 0] as bits (lg_gcn_fwd_nm_bits), which the
+    (mask_words(N, B),), else empty): [x_L > 0] as bits (lg_gcn_fwd_nm_bits), which the
     last layer's backward reads instead of gathering x_L.
     bf16: the node-major transform as one bf16 MFMA product (LG_F_BF16, the configs[2] tier).
     nodetab_s, pairs_s, pos_slot_t (ops.SensorMarks; node-major, L >= 1): x_0 stays
@@ -1136,73 +1441,39 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
         raise ValueError("gnn_trunk: skip=True runs on the node-major fp32 tier only")
     if tuple(proj_weight.shape) != (D, Ds + 1):
         raise ValueError(f"proj_weight must be (D, Ds + 1) = ({D}, {Ds + 1}), got {tuple(proj_weight.shape)}")
-    N = sensor_slot.shape[0]
-    drop = p > 0.0
-    seed_v, sbit = _seed_args(seed) if drop else (0, 0)
-    dflag = nat.LG_F_DROPOUT if drop else 0
-    st = stream_of(h_s)
-    L = len(weights)
-    nmask = N * ((B + 15) // 16) * 64
+    N, L = sensor_slot.shape[0], len(weights)
     x0c = _compress_x0(nodetab_s, node_major, L) and not skip
-    if x0c:
-        x0 = torch.empty((S, B, D), device=h_s.device, dtype=torch.float32)
-        x0bits = torch.empty(nmask, device=h_s.device, dtype=torch.int16)
-        with _timed("node_init", h_s.device):
+    t = _trunk(lib, h_s, B, N, S, D, L, p, seed, node_major=node_major, bf16=bf16, skip=skip, nnz=col.numel(),
+               nodetab=nodetab, pairs=pairs, rowptr=rowptr, col=col, w=w, nodetab_s=nodetab_s, pairs_s=pairs_s,
+               node_bias=node_bias)
+    dflag, seed_v, sbit = t.drop
+    out = _alloc(_gnn_trunk_layout(L, B, N, S, D, node_major, skip, x0c), h_s)
+    f = trunk_fields("gnn_trunk", out)
+    with _timed("node_init", t.dev):
+        if x0c:
             check(lib.lg_node_init_bits_fwd(ptr(sensor_slot), ptr(sensor_idx), ptr(h_s), ptr(proj_weight),
-                                            ptr(node_bias), ptr(x0), ptr(x0bits), B, N, S, Ds, D, dflag, p, seed_v,
-                                            0 | sbit, st), "lg_node_init_bits_fwd")
-    else:
-        x0 = torch.empty((N, B, D) if node_major else (B, N, D), device=h_s.device, dtype=torch.float32)
-        x0bits = torch.empty(0, device=h_s.device, dtype=torch.int16)
-        with _timed("node_init", h_s.device):
+                                            ptr(node_bias), ptr(f.xs[0]), ptr(f.x0bits), B, N, S, Ds, D, dflag, p,
+                                            seed_v, 0 | sbit, t.st), "lg_node_init_bits_fwd")
+        else:
             check(lib.lg_node_init_proj_fwd(ptr(sensor_slot), ptr(sensor_idx), ptr(h_s), ptr(proj_weight),
-                                            ptr(node_bias), ptr(x0), B, N, S, Ds, D,
-                                            dflag | (nat.LG_F_NODE_MAJOR if node_major else 0), p, seed_v, 0 | sbit, st),
-                  "lg_node_init_proj_fwd")
-    xs = [x0]
-    ymask = torch.empty((nmask * (L if skip else 1)) if (node_major and L > 0) else 0, device=h_s.device,
-                        dtype=torch.int16)
+                                            ptr(node_bias), ptr(f.xs[0]), B, N, S, Ds, D,
+                                            dflag | (nat.LG_F_NODE_MAJOR if node_major else 0), p, seed_v, 0 | sbit,
+                                            t.st), "lg_node_init_proj_fwd")
     for l, (W, b) in enumerate(zip(weights, biases)):
-        y = torch.empty((N, B, D), device=h_s.device, dtype=torch.float32) if node_major else torch.empty_like(x0)
-        flags = nat.LG_F_BIAS | nat.LG_F_RELU | dflag | (nat.LG_F_BF16 if bf16 else 0)
-        with _timed("gcn_fwd" if not (x0c and l == 0) else "gcn_fwd_l0", h_s.device):
-            if x0c and l == 0:
-                check(lib.lg_gcn_fwd_nm_x0(ptr(nodetab_s), ptr(pairs_s), ptr(x0), ptr(x0bits), ptr(node_bias),
-                                           ptr(W), ptr(b), ptr(y), B, N, S, D, flags | GCN_FWD_NM_EXTRA_FLAGS, p,
-                                           seed_v, (l + 1) | sbit, st), "lg_gcn_fwd_nm_x0")
-            elif skip:
-                check(lib.lg_gcn_fwd_nm_skip(ptr(nodetab), ptr(pairs), ptr(xs[-1]), ptr(W), ptr(b), ptr(y), B, N,
-                                             D, col.numel(), flags | (GCN_FWD_NM_EXTRA_FLAGS & nat.LG_F_BF16X3), p,
-                                             seed_v, (l + 1) | sbit, st, ptr(ymask[l * nmask:(l + 1) * nmask])),
-                      "lg_gcn_fwd_nm_skip")
-            elif node_major:
-                fx = GCN_FWD_DENSE_EXTRA_FLAGS if not bf16 else 0
-                check(lib.lg_gcn_fwd_nm_bits(ptr(nodetab), ptr(pairs), ptr(xs[-1]), ptr(W), ptr(b), ptr(y), B, N,
-                                             D, col.numel(), flags | GCN_FWD_NM_EXTRA_FLAGS | fx, p, seed_v,
-                                             (l + 1) | sbit, st, ptr(ymask) if l == L - 1 else None),
-                      "lg_gcn_fwd_nm_bits")
-            else:
-                check(lib.lg_gcn_fwd(ptr(rowptr), ptr(col), ptr(w), ptr(xs[-1]), ptr(W), ptr(b), ptr(y), B, N, D,
-                                     col.numel(), flags, p, seed_v, (l + 1) | sbit, st), "lg_gcn_fwd")
-        xs.append(y)
-    return xs + [ymask, x0bits]
+        words = _layer_words(f.ymask, l, L) if skip else f.ymask if (node_major and l == L - 1) else None
+        _layer_forward(t, l, f.xs[l], W, b, f.xs[l + 1], words, x0bits=f.x0bits if (x0c and l == 0) else None,
+                       branch=skip)
+    return out
 
 
 @gnn_trunk.register_fake
 def _(h_s, proj_weight, node_bias, weights, biases, sensor_slot, sensor_idx, nonsensor_idx, slot_live, nodetab, pairs,
       rowptr, col, w, nodetab_t, pairs_t, rowptr_t, col_t, w_t, p, node_major, seed, nodetab_s, pairs_s, pos_slot_t,
       edge_w=None, *, bf16=False, skip=False):
-    B, S = h_s.shape[0], h_s.shape[1]
-    D = proj_weight.shape[0]
-    N = sensor_slot.shape[0]
-    shape = (N, B, D) if node_major else (B, N, D)
     L = len(weights)
-    nmask = N * ((B + 15) // 16) * 64 if (node_major and L > 0) else 0
     x0c = _compress_x0(nodetab_s, node_major, L) and not skip
-    x0 = h_s.new_empty((S, B, D)) if x0c else h_s.new_empty(shape)
-    return ([x0] + [h_s.new_empty(shape) for _ in range(L)]
-            + [h_s.new_empty((nmask * (L if skip else 1),), dtype=torch.int16)]
-            + [h_s.new_empty((nmask if x0c else 0,), dtype=torch.int16)])
+    return _alloc(_gnn_trunk_layout(L, h_s.shape[0], sensor_slot.shape[0], h_s.shape[1], proj_weight.shape[0],
+                                    node_major, skip, x0c), h_s)
 
 
 @torch.library.custom_op(f"{NS}::gnn_trunk_backward", mutates_args=(), device_types="cuda")
@@ -1226,167 +1497,18 @@ def gnn_trunk_backward(grad_out: Tensor, xs: List[Tensor], ymask: Tensor, h_s: T
     words of ymask)."""
     lib = load_library()
     L = len(weights)
-    dev = grad_out.device
-    st = stream_of(grad_out)
-    if node_major:
-        N, B, D = xs[-1].shape
-    else:
-        B, N, D = xs[0].shape
-    S, Ds = h_s.shape[1], h_s.shape[2]
-    scale = 1.0 / (1.0 - p) if p > 0.0 else 1.0
-    dy = grad_out.contiguous()
-    wgrad = _WGrad(rowptr, col) if rowptr is not None else None
-    wsb = lib.lg_gcn_bwd_nm_workspace_bytes(D) if node_major else lib.lg_gcn_bwd_workspace_bytes(D)
-    # one workspace per layer: the layers' slab reductions run together at the batch flush
-    wss = [torch.empty(int(wsb), device=dev, dtype=torch.uint8) for _ in range(L)]
-    dWs: List[Tensor] = [grad_out] * L
-    dbs: List[Tensor] = [grad_out] * L
-    dbias_ns = torch.empty(D, device=dev, dtype=torch.float32)
-    with _reduce_batch(lib, st):
-        dh_s, dWp, dbp = _trunk_backward_launches(lib, dy, xs, ymask, h_s, proj_weight, weights, sensor_slot, sensor_idx,
-                                                  nonsensor_idx, slot_live, nodetab_t, pairs_t, rowptr_t, col_t, w_t,
-                                                  node_major, bf16, scale, wss, dWs, dbs, dbias_ns, st,
-                                                  (x0bits, x0_bias, pos_slot_t) if x0bits is not None else None, p,
-                                                  wgrad, skip)
-    return dh_s, dWp, dbp, dWs, dbs, (wgrad.total(dev) if wgrad is not None else torch.empty(0, device=dev))
-
-
-def _trunk_backward_launches(lib, dy, xs, ymask, h_s, proj_weight, weights, sensor_slot, sensor_idx, nonsensor_idx, slot_live,
-                             nodetab_t, pairs_t, rowptr_t, col_t, w_t, node_major, bf16, scale, wss, dWs, dbs, dbias_ns,
-                             st, x0c=None, p=0.0, wgrad=None, skip=False):
-    dy = _trunk_layer_launches(lib, dy, xs, ymask, weights, sensor_slot, nodetab_t, pairs_t, rowptr_t, col_t, w_t,
-                               node_major, bf16, scale, wss, dWs, dbs, dbias_ns, st, x0c, p, wgrad, skip)
-    L = len(weights)
-    if node_major:
-        N, B, D = xs[-1].shape
-    else:
-        B, N, D = xs[0].shape
-    if L == 0:  # no layer-0 launch applied the node init's relu/dropout mask
-        dy = dy * (xs[0] > 0) * scale
-        dbias_ns = dy.index_select(0 if node_major else 1, nonsensor_idx).sum(dim=(0, 1))
-    return _sensor_proj_backward(lib, dy, h_s, proj_weight, sensor_idx, slot_live, dbias_ns, B, N, D, node_major, wss, st)
-
-
-def _sensor_proj_backward(lib, dy, h_s, proj_weight, sensor_idx, slot_live, dbias_ns, B, N, D, node_major, wss, st):
-    """(dh_s, dproj_weight, dnode_bias) from the node init's pre-activation gradient dy (ONE
-    lg_sensor_proj_bwd) and the non-sensor rows' bias sum dbias_ns.  The workspace joins wss."""
-    dev = dy.device
-    S, Ds = h_s.shape[1], h_s.shape[2]
-    dh_s = torch.empty(B, S, Ds, device=dev, dtype=torch.float32)
-    dWp = torch.empty(D, Ds + 1, device=dev, dtype=torch.float32)
-    dbp = torch.empty(D, device=dev, dtype=torch.float32)
-    wsp = torch.empty(int(lib.lg_sensor_proj_bwd_workspace_bytes(B, S, Ds, D)), device=dev, dtype=torch.uint8)
-    wss.append(wsp)  # held by the caller until the reduce batch is flushed
-    with _timed("linear_dw", dev):
-        check(lib.lg_sensor_proj_bwd(ptr(dy), ptr(sensor_idx), ptr(slot_live) if slot_live is not None else None,
-                                     ptr(h_s), ptr(proj_weight), ptr(dbias_ns), ptr(dh_s), ptr(dWp), ptr(dbp), B, N,
-                                     S, Ds, D, nat.LG_F_NODE_MAJOR if node_major else 0, ptr(wsp), wsp.numel(), st),
-              "lg_sensor_proj_bwd")
-    return dh_s, dWp, dbp
-
-
-class _WGrad:
-    """dL/dw of the trunk's layers, collected by _trunk_layer_launches when the edge coefficients
-    learn: G = sum over the layers of _layer_dw, added in the order the backward visits them
-    (last layer first), over the slots of the forward CSR (rowptr, col)."""
-
-    def __init__(self, rowptr: Tensor, col: Tensor):
-        self.rowptr, self.col, self.G = rowptr, col, None
-
-    def add(self, G: Tensor) -> None:
-        self.G = G if self.G is None else self.G + G
-
-    def total(self, dev) -> Tensor:
-        return self.G if self.G is not None else torch.zeros(self.col.numel(), device=dev)
-
-
-def _layer_dw(dy: Tensor, xs, ymask: Tensor, W: Tensor, l: int, L: int, node_major: bool, scale: float,
-              rowptr: Tensor, col: Tensor, x0c, sensor_slot: Tensor, p: float, skip: bool = False) -> Tensor:
-    """Layer l's share of dL/dw: G_l[k] = sum_b (dz W_l)[n, b] . x_l[col k, b] for every slot k of
-    row n, with dz = dy * scale * [x_{l+1} > 0] on the last layer and dz = dy on the others (their dy
-    is the layer above's dx, which that launch already masked: LG_F_MASK_OUT), exactly the dz of
-    the layer's own backward launch.  Node-major: lg_sddmm_nm (the last layer's mask from the bit
-    words when the forward wrote them); the compressed node init is materialised for layer 0
-    (lg_node_init_expand; a compressed-x0 form of the kernel is left for later).  Window-major:
-    da on a library GEMM, then ONE lg_sddmm_cols over the [N][B * D] transposes.  Deterministic.
-    skip: dy is the gradient of x_{l+1} = x_l + f_l, no launch masked it, and every layer's dz is
-    dy * scale * [f_l > 0] from the layer's own words of ymask."""
-    last = l == L - 1
-    if skip:
-        nmask = ymask.numel() // L
-        return sddmm_nm(rowptr, col, dy, W, xs[l], ymask=ymask[l * nmask:(l + 1) * nmask], mask_in=True, scale=scale)
-    if node_major:
-        x = xs[l]
-        if x0c is not None and l == 0:
-            x0bits, node_bias, _ = x0c
-            x = expand_x0(xs[0], x0bits, sensor_slot, node_bias, dy.shape[0], p)
-        bits = ymask if (last and ymask.numel() > 0) else None
-        return sddmm_nm(rowptr, col, dy, W, x, y=xs[l + 1] if (last and bits is None) else None, ymask=bits,
-                        mask_in=last, scale=scale)
-    B, N, D = dy.shape
-    dz = dy * (xs[l + 1] > 0) * scale if last else dy
-    with torch.autocast("cuda", enabled=False):
-        da = (dz.reshape(B * N, D) @ W).view(B, N, D)
-    return torch.ops.leakgnn.sddmm_cols(rowptr, col, da.transpose(0, 1).reshape(N, B * D),
-                                        xs[l].transpose(0, 1).reshape(N, B * D))
-
-
-def _trunk_layer_launches(lib, dy, xs, ymask, weights, sensor_slot, nodetab_t, pairs_t, rowptr_t, col_t, w_t, node_major,
-                          bf16, scale, wss, dWs, dbs, dbias_ns, st, x0c=None, p=0.0, wgrad=None, skip=False) -> Tensor:
-    """The GCN layers' backward, last first; returns the node init's pre-activation gradient
-    (layer 0's dx: masked by the node init's ReLU / dropout; node-major with the compressed
-    node init: the sensor nodes' rows only) and leaves the non-sensor rows' sum in dbias_ns.
-    wgrad (_WGrad): every layer also adds its dL/dw (_layer_dw).
-    skip: x_{l+1} = x_l + f_l, so dx_l = dx_{l+1} + (branch); every layer applies its own mask
-    (LG_F_MASK_IN on its bit words) and only layer 0 a LG_F_MASK_OUT, the node init's."""
-    L = len(weights)
-    dev = dy.device
-    if node_major:
-        N, B, D = xs[-1].shape
-    else:
-        B, N, D = xs[0].shape
-    for l in range(L - 1, -1, -1):
-        ws = wss[l]
-        flags = nat.LG_F_MASK_OUT | (nat.LG_F_MASK_IN if l == L - 1 else 0) | (nat.LG_F_BF16 if bf16 else 0)
-        if skip:
-            flags = nat.LG_F_MASK_IN | (nat.LG_F_MASK_OUT if l == 0 else 0)
-        if node_major and not bf16:
-            flags |= GCN_BWD_NM_EXTRA_FLAGS
-        if l == 0:  # lg_sensor_proj_bwd reads only the sensor rows of layer 0's dx
-            flags |= nat.LG_F_DX_SENSOR_ROWS
-        dx = torch.empty_like(dy)
-        dW = torch.empty(D, D, device=dev, dtype=torch.float32)
-        db = torch.empty(D, device=dev, dtype=torch.float32)
-        slot_p, dbias_p = (ptr(sensor_slot), ptr(dbias_ns)) if l == 0 else (None, None)
-        if wgrad is not None:
-            wgrad.add(_layer_dw(dy, xs, ymask, weights[l], l, L, node_major, scale, wgrad.rowptr, wgrad.col, x0c,
-                                sensor_slot, p, skip))
-        with _timed("gcn_bwd" if l == L - 1 else f"gcn_bwd_l{l}", dev):
-            if x0c is not None and l == 0:  # the compressed node init (xs[0]: its sensor rows, (S, B, D))
-                x0bits, node_bias, pos_slot_t = x0c
-                S = xs[0].shape[0]
-                check(lib.lg_gcn_bwd_nm_x0(ptr(nodetab_t), ptr(pairs_t), ptr(pos_slot_t), ptr(dy), ptr(xs[0]),
-                                           ptr(x0bits), ptr(node_bias), ptr(weights[0]), ptr(dx), ptr(dW), ptr(db),
-                                           slot_p, dbias_p, B, N, S, D, flags | (nat.LG_F_DROPOUT if p > 0.0 else 0),
-                                           p, scale, ptr(ws), ws.numel(), st), "lg_gcn_bwd_nm_x0")
-            elif skip:
-                nmask = ymask.numel() // L
-                check(lib.lg_gcn_bwd_nm_skip(ptr(nodetab_t), ptr(pairs_t), ptr(dy), None, ptr(xs[l]),
-                                             ptr(weights[l]), ptr(dx), ptr(dW), ptr(db), slot_p, dbias_p, B, N, D,
-                                             flags, scale, scale, ptr(ws), ws.numel(), st,
-                                             ptr(ymask[l * nmask:(l + 1) * nmask])), "lg_gcn_bwd_nm_skip")
-            elif node_major:
-                bits = ptr(ymask) if (l == L - 1 and ymask.numel() > 0) else None  # [x_L > 0] as bits
-                check(lib.lg_gcn_bwd_nm_bits(ptr(nodetab_t), ptr(pairs_t), ptr(dy), ptr(xs[l + 1]), ptr(xs[l]),
-                                             ptr(weights[l]), ptr(dx), ptr(dW), ptr(db), slot_p, dbias_p, B, N, D,
-                                             flags, scale, scale, ptr(ws), ws.numel(), st, bits), "lg_gcn_bwd_nm_bits")
-            else:
-                check(lib.lg_gcn_bwd(ptr(rowptr_t), ptr(col_t), ptr(w_t), ptr(dy), ptr(xs[l + 1]), ptr(xs[l]),
-                                     ptr(weights[l]), ptr(dx), ptr(dW), ptr(db), slot_p, dbias_p, B, N, D,
-                                     col_t.numel(), flags, scale, scale, ptr(ws), ws.numel(), st), "lg_gcn_bwd")
-        dWs[l], dbs[l] = dW, db
-        dy = dx  # already masked by the previous op's relu/dropout
-    return dy
+    N, B, D = xs[-1].shape if node_major else xs[0].transpose(0, 1).shape
+    t = _trunk(lib, grad_out, B, N, h_s.shape[1], D, L, p, node_major=node_major, bf16=bf16, skip=skip,
+               nodetab_t=nodetab_t, pairs_t=pairs_t, rowptr_t=rowptr_t, col_t=col_t, w_t=w_t, pos_slot_t=pos_slot_t,
+               sensor_slot=sensor_slot, node_bias=x0_bias)
+    wgrad = _WGrad(rowptr, col)
+    with _reduce_batch(lib, t.st):
+        dy, dWs, dbs, dbias_ns, wss = _trunk_layer_launches(t, grad_out.contiguous(), xs, ymask, weights, x0bits, wgrad)
+        if L == 0:  # no layer-0 launch applied the node init's relu/dropout mask
+            dy = dy * (xs[0] > 0) * t.scale
+            dbias_ns = dy.index_select(0 if node_major else 1, nonsensor_idx).sum(dim=(0, 1))
+        dh_s, dWp, dbp = _sensor_proj_backward(t, dy, h_s, proj_weight, sensor_idx, slot_live, dbias_ns, wss)
+    return dh_s, dWp, dbp, dWs, dbs, wgrad.total(t.dev)
 
 
 @gnn_trunk_backward.register_fake
@@ -1400,46 +1522,27 @@ def _(grad_out, xs, ymask, h_s, proj_weight, weights, sensor_slot, sensor_idx, n
 
 
 def _trunk_setup(ctx, inputs, keyword_only_inputs, output):
-    (h_s, proj_weight, node_bias, weights, biases, sensor_slot, sensor_idx, nonsensor_idx, slot_live, _, _, rowptr, col,
-     _, nodetab_t, pairs_t, rowptr_t, col_t, w_t, p, node_major, _, _, _, pos_slot_in, edge_w) = inputs
-    bf16 = bool(keyword_only_inputs.get("bf16", False))
-    ctx.skip = bool(keyword_only_inputs.get("skip", False))
-    # learned edge weights (requires_grad, not needs_input_grad: that tuple is flat over the tensor lists here)
-    ctx.w_grad = edge_w is not None and edge_w.requires_grad
-    # the dispatcher drops trailing arguments that equal their defaults before autograd sees
-    # them, and the backward returns one entry per argument it saw
-    ctx.n_in = 26 if edge_w is not None else 25
+    a, f = _trunk_ctx(ctx, gnn_trunk, inputs, output)
+    bf16, skip = bool(keyword_only_inputs.get("bf16", False)), bool(keyword_only_inputs.get("skip", False))
     if ctx.w_grad and bf16:
         raise NotImplementedError("gnn_trunk: the gradient of edge_w exists on the fp32 tier only")
-    ctx.L = len(weights)
-    ctx.bf16 = bf16
-    ctx.x0c = output[ctx.L + 2].numel() > 0  # x_0 compressed (x0bits non-empty)
-    # x_0 .. x_{L-1} (returned for the backward's masks), ymask and x0bits
-    ctx.mark_non_differentiable(*output[:ctx.L], output[ctx.L + 1], output[ctx.L + 2])
-    ctx.set_materialize_grads(False)  # their gradients would be zero-filled (B, N, D) tensors
-    ctx.p, ctx.node_major, ctx.has_live = p, node_major, slot_live is not None
-    pos_slot_t = pos_slot_in if ctx.x0c else sensor_slot
-    ctx.save_for_backward(*output, h_s, proj_weight, *weights, sensor_slot, sensor_idx, nonsensor_idx,
-                          slot_live if slot_live is not None else sensor_slot, nodetab_t, pairs_t, rowptr_t, col_t, w_t,
-                          node_bias, pos_slot_t, *((rowptr, col) if ctx.w_grad else ()))
+    x0c = f.x0bits.numel() > 0  # x_0 compressed
+    ctx.kw = dict(p=a["p"], node_major=a["node_major"], bf16=bf16, skip=skip)
+    # x_0 .. x_L and ymask as returned; the arguments of gnn_trunk_backward by name
+    _save_named(ctx, xs=f.xs, ymask=f.ymask, rowptr=a["rowptr"] if ctx.w_grad else None,
+                col=a["col"] if ctx.w_grad else None, x0bits=f.x0bits if x0c else None,
+                x0_bias=a["node_bias"] if x0c else None, pos_slot_t=a["pos_slot_t"] if x0c else None,
+                **{k: a[k] for k in ("h_s", "proj_weight", "weights", "sensor_slot", "sensor_idx", "nonsensor_idx",
+                                     "slot_live", "nodetab_t", "pairs_t", "rowptr_t", "col_t", "w_t")})
 
 
 def _trunk_bwd(ctx, grads):
-    L = ctx.L
-    saved = ctx.saved_tensors
-    xs, ymask, x0bits, h_s, proj_weight = list(saved[:L + 1]), saved[L + 1], saved[L + 2], saved[L + 3], saved[L + 4]
-    weights = list(saved[L + 5:2 * L + 5])
-    (sensor_slot, sensor_idx, nonsensor_idx, live, nodetab_t, pairs_t, rowptr_t, col_t, w_t, node_bias,
-     pos_slot_t) = saved[2 * L + 5:2 * L + 16]
-    rowptr, col = saved[2 * L + 16:] if ctx.w_grad else (None, None)
-    g = grads[L]
+    g = grads[ctx.h]
     if g is None:
-        return (None,) * ctx.n_in
-    dh_s, dWp, dbp, dWs, dbs, dw = torch.ops.leakgnn.gnn_trunk_backward(
-        g, xs, ymask, h_s, proj_weight, weights, sensor_slot, sensor_idx, nonsensor_idx, live if ctx.has_live else None,
-        nodetab_t, pairs_t, rowptr_t, col_t, w_t, ctx.p, ctx.node_major, x0bits if ctx.x0c else None,
-        node_bias if ctx.x0c else None, pos_slot_t if ctx.x0c else None, rowptr, col, bf16=ctx.bf16, skip=ctx.skip)
-    return ((dh_s, dWp, dbp, dWs, dbs) + (None,) * 20 + (dw if ctx.w_grad else None,))[:ctx.n_in]
+        return _named_grads(gnn_trunk, ctx.n_in)
+    dh_s, dWp, dbp, dWs, dbs, dw = torch.ops.leakgnn.gnn_trunk_backward(g, **_saved_named(ctx), **ctx.kw)
+    return _named_grads(gnn_trunk, ctx.n_in, h_s=dh_s, proj_weight=dWp, node_bias=dbp, weights=dWs, biases=dbs,
+                        edge_w=dw if ctx.w_grad else None)
 
 
 gnn_trunk.register_autograd(_trunk_bwd, setup_context=_trunk_setup)
@@ -1489,44 +1592,29 @@ def gnn_trunk_norm(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights:
     if tuple(proj_weight.shape) != (D, Ds + 1):
         raise ValueError(f"proj_weight must be (D, Ds + 1) = ({D}, {Ds + 1}), got {tuple(proj_weight.shape)}")
     N = sensor_slot.shape[0]
-    dev = h_s.device
-    drop = p > 0.0
-    seed_v, sbit = _seed_args(seed) if drop else (0, 0)
-    dflag = nat.LG_F_DROPOUT if drop else 0
-    st = stream_of(h_s)
-    nmask = N * ((B + 15) // 16) * 64
-    new = lambda: torch.empty((N, B, D), device=dev, dtype=torch.float32)  # noqa: E731
-    x0 = new()
+    t = _trunk(lib, h_s, B, N, S, D, L, p, seed, nnz=col.numel(), nodetab=nodetab, pairs=pairs)
+    dev, st, (dflag, seed_v, sbit) = t.dev, t.st, t.drop
+    out = _alloc(_gnn_trunk_norm_layout(L, B, N, D), h_s)
+    f = trunk_fields("gnn_trunk_norm", out)
+    xs, xns, stats = f.xs, f.xns, f.stats
     with _timed("node_init", dev):
         check(lib.lg_node_init_proj_fwd(ptr(sensor_slot), ptr(sensor_idx), ptr(h_s), ptr(proj_weight), ptr(node_bias),
-                                        ptr(x0), B, N, S, Ds, D, dflag | nat.LG_F_NODE_MAJOR, p, seed_v, 0 | sbit, st),
+                                        ptr(xs[0]), B, N, S, Ds, D, dflag | nat.LG_F_NODE_MAJOR, p, seed_v, 0 | sbit, st),
               "lg_node_init_proj_fwd")
-    stats = torch.empty((L + 1, N * B, 2), device=dev, dtype=torch.float32)
-    ymask = torch.empty(nmask * L, device=dev, dtype=torch.int16)
-    xs, xns = [x0], [new()]
     with _timed("layernorm_fwd", dev):
-        _ln_fwd(lib, x0, None, gammas[0], betas[0], None, xns[0], stats[0], eps, st)
-    flags = nat.LG_F_BIAS | nat.LG_F_RELU | dflag | (GCN_FWD_NM_EXTRA_FLAGS & nat.LG_F_BF16X3)
+        _ln_fwd(lib, xs[0], None, gammas[0], betas[0], None, xns[0], stats[0], eps, st)
     for l, (W, b) in enumerate(zip(weights, biases)):
-        f = new()
-        with _timed("gcn_fwd", dev):
-            check(lib.lg_gcn_fwd_nm_bits(ptr(nodetab), ptr(pairs), ptr(xns[l]), ptr(W), ptr(b), ptr(f), B, N, D,
-                                         col.numel(), flags, p, seed_v, (l + 1) | sbit, st,
-                                         ptr(ymask[l * nmask:(l + 1) * nmask])), "lg_gcn_fwd_nm_bits")
-        xs.append(new())
-        xns.append(new())
+        fl = torch.empty((N, B, D), device=dev, dtype=torch.float32)  # the branch's output, a temporary
+        _layer_forward(t, l, xns[l], W, b, fl, _layer_words(f.ymask, l, L), branch=True)
         with _timed("layernorm_fwd", dev):
-            _ln_fwd(lib, xs[l], f, gammas[l + 1], betas[l + 1], xs[l + 1], xns[l + 1], stats[l + 1], eps, st)
-    return [xns[L]] + xs + xns[:L] + [stats, ymask]
+            _ln_fwd(lib, xs[l], fl, gammas[l + 1], betas[l + 1], xs[l + 1], xns[l + 1], stats[l + 1], eps, st)
+    return out
 
 
 @gnn_trunk_norm.register_fake
 def _(h_s, proj_weight, node_bias, weights, biases, gammas, betas, sensor_slot, sensor_idx, nonsensor_idx, slot_live,
       nodetab, pairs, rowptr, col, nodetab_t, pairs_t, p, eps, seed, edge_w=None):
-    B, D, N, L = h_s.shape[0], proj_weight.shape[0], sensor_slot.shape[0], len(weights)
-    nmask = N * ((B + 15) // 16) * 64
-    return ([h_s.new_empty((N, B, D)) for _ in range(2 * L + 2)] + [h_s.new_empty((L + 1, N * B, 2))]
-            + [h_s.new_empty((nmask * L,), dtype=torch.int16)])
+    return _alloc(_gnn_trunk_norm_layout(len(weights), h_s.shape[0], sensor_slot.shape[0], proj_weight.shape[0]), h_s)
 
 
 @torch.library.custom_op(f"{NS}::gnn_trunk_norm_backward", mutates_args=(), device_types="cuda")
@@ -1548,13 +1636,10 @@ def gnn_trunk_norm_backward(grad_out: Tensor, xs: List[Tensor], xns: List[Tensor
     learn; layer l's share is lg_sddmm_nm on (a_{l+1}, xn_l, the layer's words)."""
     lib = load_library()
     L = len(weights)
-    dev = grad_out.device
-    st = stream_of(grad_out)
     N, B, D = xs[0].shape
-    rows = N * B
-    scale = 1.0 / (1.0 - p) if p > 0.0 else 1.0
-    nmask = ymask.numel() // L if L else 0
-    wgrad = _WGrad(rowptr, col) if rowptr is not None else None
+    t = _trunk(lib, grad_out, B, N, h_s.shape[1], D, L, p, nodetab_t=nodetab_t, pairs_t=pairs_t)
+    dev, st, scale, rows = t.dev, t.st, t.scale, N * B
+    wgrad = _WGrad(rowptr, col)
     lnb, gcb = int(lib.lg_layernorm_bwd_workspace_bytes(D)), int(lib.lg_gcn_bwd_nm_workspace_bytes(D))
     wss: List[Tensor] = []  # every workspace lives until the reduce batch is flushed
 
@@ -1573,34 +1658,18 @@ def gnn_trunk_norm_backward(grad_out: Tensor, xs: List[Tensor], xns: List[Tensor
         dgs[l], dbts[l] = dg, dbt
         return dx
 
-    dWs: List[Tensor] = [grad_out] * L
-    dbs: List[Tensor] = [grad_out] * L
-    dgs: List[Tensor] = [grad_out] * (L + 1)
-    dbts: List[Tensor] = [grad_out] * (L + 1)
+    dWs, dbs, dgs, dbts = ([grad_out] * n for n in (L, L, L + 1, L + 1))
     with _reduce_batch(lib, st):
         a = ln_bwd(L, grad_out.contiguous(), None)
         for l in range(L - 1, -1, -1):
-            words = ymask[l * nmask:(l + 1) * nmask]
-            if wgrad is not None:
-                wgrad.add(sddmm_nm(wgrad.rowptr, wgrad.col, a, weights[l], xns[l], ymask=words, mask_in=True,
-                                   scale=scale))
-            dxn = torch.empty_like(a)
-            dW = torch.empty(D, D, device=dev, dtype=torch.float32)
-            db = torch.empty(D, device=dev, dtype=torch.float32)
-            w = ws(gcb)
-            with _timed("gcn_bwd" if l == L - 1 else f"gcn_bwd_l{l}", dev):
-                check(lib.lg_gcn_bwd_nm_bits(ptr(nodetab_t), ptr(pairs_t), ptr(a), None, ptr(xns[l]), ptr(weights[l]),
-                                             ptr(dxn), ptr(dW), ptr(db), None, None, B, N, D,
-                                             nat.LG_F_MASK_IN | GCN_BWD_NM_EXTRA_FLAGS, scale, 1.0, ptr(w), w.numel(),
-                                             st, ptr(words)), "lg_gcn_bwd_nm_bits")
-            dWs[l], dbs[l] = dW, db
+            # the branch's input xn_l is a norm's output, not a ReLU's: no mask_out, no rescale of dxn
+            dxn, dWs[l], dbs[l] = _layer_backward(t, l, a, xns[l], None, weights[l], _layer_words(ymask, l, L), ws(gcb),
+                                                  mask_in=True, mask_out=False, scale_out=1.0, wgrad=wgrad)
             a = ln_bwd(l, dxn, a)
         # a: the node init's pre-activation gradient; its non-sensor rows' sum is the bias's share
         dbias_ns = a.index_select(0, nonsensor_idx).sum(dim=(0, 1))
-        dh_s, dWp, dbp = _sensor_proj_backward(lib, a, h_s, proj_weight, sensor_idx, slot_live, dbias_ns, B, N, D,
-                                               True, wss, st)
-    return (dh_s, dWp, dbp, dWs, dbs, dgs, dbts,
-            wgrad.total(dev) if wgrad is not None else torch.empty(0, device=dev))
+        dh_s, dWp, dbp = _sensor_proj_backward(t, a, h_s, proj_weight, sensor_idx, slot_live, dbias_ns, wss)
+    return dh_s, dWp, dbp, dWs, dbs, dgs, dbts, wgrad.total(dev)
 
 
 @gnn_trunk_norm_backward.register_fake
@@ -1614,36 +1683,23 @@ def _(grad_out, xs, xns, stats, ymask, h_s, proj_weight, weights, gammas, sensor
 
 
 def _trunk_norm_setup(ctx, inputs, output):
-    (h_s, proj_weight, _, weights, _, gammas, _, sensor_slot, sensor_idx, nonsensor_idx, slot_live, _, _, rowptr, col,
-     nodetab_t, pairs_t, p, _, _, edge_w) = inputs
-    ctx.w_grad = edge_w is not None and edge_w.requires_grad
-    ctx.n_in = 21 if edge_w is not None else 20  # the dispatcher drops a trailing default (see _trunk_setup)
-    L = ctx.L = len(weights)
-    ctx.mark_non_differentiable(*output[1:])
-    ctx.set_materialize_grads(False)
-    ctx.p, ctx.has_live = p, slot_live is not None
-    ctx.save_for_backward(*output[1:], h_s, proj_weight, *weights, *gammas, sensor_slot, sensor_idx, nonsensor_idx,
-                          slot_live if slot_live is not None else sensor_slot, nodetab_t, pairs_t,
-                          *((rowptr, col) if ctx.w_grad else ()))
-    assert len(output) == 2 * L + 4
+    a, f = _trunk_ctx(ctx, gnn_trunk_norm, inputs, output)
+    ctx.kw = dict(p=a["p"])
+    # the arguments of gnn_trunk_norm_backward by name (xns: xn_0 .. xn_{L-1}, the branches' inputs)
+    _save_named(ctx, xs=f.xs, xns=f.xns[:-1], stats=f.stats, ymask=f.ymask,
+                rowptr=a["rowptr"] if ctx.w_grad else None, col=a["col"] if ctx.w_grad else None,
+                **{k: a[k] for k in ("h_s", "proj_weight", "weights", "gammas", "sensor_slot", "sensor_idx",
+                                     "nonsensor_idx", "slot_live", "nodetab_t", "pairs_t")})
 
 
 def _trunk_norm_bwd(ctx, grads):
-    L = ctx.L
-    sv = ctx.saved_tensors
-    g = grads[0]
+    g = grads[ctx.h]
     if g is None:
-        return (None,) * ctx.n_in
-    xs, xns, stats, ymask = list(sv[:L + 1]), list(sv[L + 1:2 * L + 1]), sv[2 * L + 1], sv[2 * L + 2]
-    k = 2 * L + 3
-    h_s, proj_weight = sv[k], sv[k + 1]
-    weights, gammas = list(sv[k + 2:k + 2 + L]), list(sv[k + 2 + L:k + 3 + 2 * L])
-    sensor_slot, sensor_idx, nonsensor_idx, live, nodetab_t, pairs_t = sv[k + 3 + 2 * L:k + 9 + 2 * L]
-    rowptr, col = sv[k + 9 + 2 * L:] if ctx.w_grad else (None, None)
+        return _named_grads(gnn_trunk_norm, ctx.n_in)
     dh_s, dWp, dbp, dWs, dbs, dgs, dbts, dw = torch.ops.leakgnn.gnn_trunk_norm_backward(
-        g, xs, xns, stats, ymask, h_s, proj_weight, weights, gammas, sensor_slot, sensor_idx, nonsensor_idx,
-        live if ctx.has_live else None, nodetab_t, pairs_t, ctx.p, rowptr, col)
-    return ((dh_s, dWp, dbp, dWs, dbs, dgs, dbts) + (None,) * 13 + (dw if ctx.w_grad else None,))[:ctx.n_in]
+        g, **_saved_named(ctx), **ctx.kw)
+    return _named_grads(gnn_trunk_norm, ctx.n_in, h_s=dh_s, proj_weight=dWp, node_bias=dbp, weights=dWs, biases=dbs,
+                        gammas=dgs, betas=dbts, edge_w=dw if ctx.w_grad else None)
 
 
 gnn_trunk_norm.register_autograd(_trunk_norm_bwd, setup_context=_trunk_norm_setup)
@@ -1691,52 +1747,28 @@ def encoder_trunk(residual: Tensor, tfeat: Optional[Tensor], w_ih: Tensor, w_hh:
     weights, biases = [_c(t) for t in weights], [_c(t) for t in biases]
     _req(residual, tfeat, w_ih, w_hh, b_ih, b_hh, proj_weight, node_bias, *weights, *biases)
     B, Lw, S = residual.shape
-    G, I = w_ih.shape
-    H = w_hh.shape[1]
-    D = proj_weight.shape[0]
-    N = sensor_slot.shape[0]
-    L = len(weights)
+    I, H, D, N, L = w_ih.shape[1], w_hh.shape[1], proj_weight.shape[0], sensor_slot.shape[0], len(weights)
     if not encoder_trunk_supported(B, N, H, D, L, True, True):
         raise NotImplementedError("encoder_trunk: node-major trunk with the compressed node init, "
                                   "node_hidden == sensor_hidden in {32, 64}, at least two layers")
     if tuple(proj_weight.shape) != (D, H + 1):
         raise ValueError(f"proj_weight must be ({D}, {H + 1}), got {tuple(proj_weight.shape)}")
-    dev = residual.device
-    st = stream_of(residual)
-    drop = p > 0.0
-    seed_v, sbit = _seed_args(seed) if drop else (0, 0)
-    dflag = nat.LG_F_DROPOUT if drop else 0
-    nmask = N * ((B + 15) // 16) * 64
-    # the fused pair's saved steps: private to lg_gru_node_init_fwd / _bwd, in 16-sequence blocks
-    rows = _gru_ni_rows(B * S)
-    h_seq = torch.empty(Lw, rows, H, device=dev) if save else torch.empty(0, device=dev)
-    gates = torch.empty(Lw, rows, 4, H, device=dev) if save else torch.empty(0, device=dev)
+    t = _trunk(lib, residual, B, N, S, D, L, p, seed, bf16=bf16, nnz=pairs.shape[0], nodetab=nodetab, pairs=pairs,
+               nodetab_s=nodetab_s, pairs_s=pairs_s, node_bias=node_bias)
+    dev, (dflag, seed_v, sbit) = t.dev, t.drop
+    out = _alloc(_encoder_trunk_layout(L, B, N, S, D, Lw, H, save), residual)
+    f = trunk_fields("encoder_trunk", out)
     h_last = torch.empty(B, S, H, device=dev)
-    xs0 = torch.empty((S, B, D), device=dev, dtype=torch.float32)
-    x0bits = torch.empty(nmask, device=dev, dtype=torch.int16)
     with _timed("gru_fwd", dev):
         check(lib.lg_gru_node_init_fwd(ptr(residual), ptr(tfeat), ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh),
-                                       ptr(h_seq) if save else None, ptr(gates) if save else None, ptr(h_last),
-                                       ptr(sensor_slot), ptr(sensor_idx), ptr(proj_weight), ptr(node_bias), ptr(xs0),
-                                       ptr(x0bits), B, Lw, S, I, H, N, dflag, p, seed_v, 0 | sbit, st),
+                                       ptr(f.h_seq) if save else None, ptr(f.gates) if save else None, ptr(h_last),
+                                       ptr(sensor_slot), ptr(sensor_idx), ptr(proj_weight), ptr(node_bias), ptr(f.xs[0]),
+                                       ptr(f.x0bits), B, Lw, S, I, H, N, dflag, p, seed_v, 0 | sbit, t.st),
               "lg_gru_node_init_fwd")
-    ymask = torch.empty(nmask, device=dev, dtype=torch.int16)
-    xs = [xs0]
     for l, (W, b) in enumerate(zip(weights, biases)):
-        y = torch.empty((N, B, D), device=dev, dtype=torch.float32)
-        flags = nat.LG_F_BIAS | nat.LG_F_RELU | dflag | (nat.LG_F_BF16 if bf16 else 0)
-        with _timed("gcn_fwd" if l > 0 else "gcn_fwd_l0", dev):
-            if l == 0:
-                check(lib.lg_gcn_fwd_nm_x0(ptr(nodetab_s), ptr(pairs_s), ptr(xs0), ptr(x0bits), ptr(node_bias), ptr(W),
-                                           ptr(b), ptr(y), B, N, S, D, flags | GCN_FWD_NM_EXTRA_FLAGS, p, seed_v,
-                                           (l + 1) | sbit, st), "lg_gcn_fwd_nm_x0")
-            else:
-                fx = GCN_FWD_DENSE_EXTRA_FLAGS if not bf16 else 0
-                check(lib.lg_gcn_fwd_nm_bits(ptr(nodetab), ptr(pairs), ptr(xs[-1]), ptr(W), ptr(b), ptr(y), B, N, D,
-                                             pairs.shape[0], flags | GCN_FWD_NM_EXTRA_FLAGS | fx, p, seed_v, (l + 1) | sbit,
-                                             st, ptr(ymask) if l == L - 1 else None), "lg_gcn_fwd_nm_bits")
-        xs.append(y)
-    return xs[1:] + [ymask, xs0, x0bits, h_seq, gates]
+        _layer_forward(t, l, f.xs[l], W, b, f.xs[l + 1], f.ymask if l == L - 1 else None,
+                       x0bits=f.x0bits if l == 0 else None)
+    return out
 
 
 @encoder_trunk.register_fake
@@ -1744,15 +1776,8 @@ def _(residual, tfeat, w_ih, w_hh, b_ih, b_hh, proj_weight, node_bias, weights, 
       slot_live, nodetab, pairs, nodetab_t, pairs_t, nodetab_s, pairs_s, pos_slot_t, p, seed, save, edge_w=None,
       rowptr=None, col=None, *, bf16=False):
     B, Lw, S = residual.shape
-    H = w_hh.shape[1]
-    D = proj_weight.shape[0]
-    N = sensor_slot.shape[0]
-    nmask = N * ((B + 15) // 16) * 64
-    rows = _gru_ni_rows(B * S)
-    h_seq = residual.new_empty(Lw, rows, H) if save else residual.new_empty(0)
-    gates = residual.new_empty(Lw, rows, 4, H) if save else residual.new_empty(0)
-    return ([residual.new_empty(N, B, D) for _ in weights] + [residual.new_empty((nmask,), dtype=torch.int16),
-            residual.new_empty(S, B, D), residual.new_empty((nmask,), dtype=torch.int16), h_seq, gates])
+    return _alloc(_encoder_trunk_layout(len(weights), B, sensor_slot.shape[0], S, proj_weight.shape[0], Lw,
+                                        w_hh.shape[1], save), residual)
 
 
 @torch.library.custom_op(f"{NS}::encoder_trunk_backward", mutates_args=(), device_types="cuda")
@@ -1770,34 +1795,25 @@ def encoder_trunk_backward(grad_out: Tensor, xs: List[Tensor], ymask: Tensor, x0
     if h_seq.numel() == 0 or gates.numel() == 0:
         raise RuntimeError("encoder_trunk was run with save=False; no backward")
     L = len(weights)
-    dev = grad_out.device
-    st = stream_of(grad_out)
     N, B, D = xs[-1].shape
     S, Lw = residual.shape[2], residual.shape[1]
     I, H = w_ih.shape[1], w_hh.shape[1]
-    scale = 1.0 / (1.0 - p) if p > 0.0 else 1.0
-    wsb = lib.lg_gcn_bwd_nm_workspace_bytes(D)
-    wss = [torch.empty(int(wsb), device=dev, dtype=torch.uint8) for _ in range(L)]
-    dWs: List[Tensor] = [grad_out] * L
-    dbs: List[Tensor] = [grad_out] * L
-    dbias_ns = torch.empty(D, device=dev, dtype=torch.float32)
+    t = _trunk(lib, grad_out, B, N, S, D, L, p, bf16=bf16, nodetab_t=nodetab_t, pairs_t=pairs_t, pos_slot_t=pos_slot_t,
+               sensor_slot=sensor_slot, node_bias=node_bias)
+    dev = t.dev
     dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
     db_ih, db_hh = torch.empty(3 * H, device=dev), torch.empty(3 * H, device=dev)
     dWp, dbp = torch.empty_like(proj_weight), torch.empty(D, device=dev)
     wsg = torch.empty(int(lib.lg_gru_node_init_bwd_workspace_bytes(B, S, I, H)), device=dev, dtype=torch.uint8)
-    wgrad = _WGrad(rowptr, col) if rowptr is not None else None
-    with _reduce_batch(lib, st):
-        dx0 = _trunk_layer_launches(lib, grad_out.contiguous(), xs, ymask, weights, sensor_slot, nodetab_t, pairs_t,
-                                    None, None, None, True, bf16, scale, wss, dWs, dbs, dbias_ns, st,
-                                    (x0bits, node_bias, pos_slot_t), p, wgrad)
+    wgrad = _WGrad(rowptr, col)
+    with _reduce_batch(lib, t.st):
+        dx0, dWs, dbs, dbias_ns, wss = _trunk_layer_launches(t, grad_out.contiguous(), xs, ymask, weights, x0bits, wgrad)
         with _timed("gru_bwd", dev):
             check(lib.lg_gru_node_init_bwd(ptr(residual), ptr(tfeat), ptr(w_ih), ptr(w_hh), ptr(h_seq), ptr(gates),
-                                           ptr(dx0), ptr(sensor_idx), ptr(slot_live) if slot_live is not None else None,
-                                           ptr(proj_weight), ptr(dbias_ns), ptr(dw_ih), ptr(dw_hh), ptr(db_ih),
-                                           ptr(db_hh), ptr(dWp), ptr(dbp), B, Lw, S, I, H, N, ptr(wsg), wsg.numel(),
-                                           st), "lg_gru_node_init_bwd")
-    return ([dw_ih, dw_hh, db_ih, db_hh, dWp, dbp] + dWs + dbs
-            + [wgrad.total(dev) if wgrad is not None else torch.empty(0, device=dev)])
+                                           ptr(dx0), ptr(sensor_idx), ptr(slot_live), ptr(proj_weight), ptr(dbias_ns),
+                                           ptr(dw_ih), ptr(dw_hh), ptr(db_ih), ptr(db_hh), ptr(dWp), ptr(dbp), B, Lw, S,
+                                           I, H, N, ptr(wsg), wsg.numel(), t.st), "lg_gru_node_init_bwd")
+    return [dw_ih, dw_hh, db_ih, db_hh, dWp, dbp] + dWs + dbs + [wgrad.total(dev)]
 
 
 @encoder_trunk_backward.register_fake
@@ -1812,47 +1828,27 @@ def _(grad_out, xs, ymask, x0bits, residual, tfeat, w_ih, w_hh, h_seq, gates, pr
 
 
 def _et_setup(ctx, inputs, keyword_only_inputs, output):
-    (residual, tfeat, w_ih, w_hh, b_ih, b_hh, proj_weight, node_bias, weights, biases, sensor_slot, sensor_idx,
-     slot_live, nodetab, pairs, nodetab_t, pairs_t, nodetab_s, pairs_s, pos_slot_t, p, seed, save, edge_w, rowptr,
-     col) = inputs
-    L = len(weights)
-    ctx.L, ctx.p, ctx.bf16 = L, p, bool(keyword_only_inputs.get("bf16", False))
-    ctx.w_grad = edge_w is not None and edge_w.requires_grad  # learned edge weights (as gnn_trunk)
-    # trailing arguments equal to their defaults never reach autograd (see _trunk_setup)
-    ctx.n_in = 26 - (3 if (edge_w is None and rowptr is None and col is None) else
-                     2 if (rowptr is None and col is None) else 1 if col is None else 0)
-    if ctx.w_grad and (ctx.bf16 or rowptr is None or col is None):
+    a, f = _trunk_ctx(ctx, encoder_trunk, inputs, output)
+    bf16 = bool(keyword_only_inputs.get("bf16", False))
+    if ctx.w_grad and (bf16 or a["rowptr"] is None or a["col"] is None):
         raise NotImplementedError("encoder_trunk: the gradient of edge_w needs rowptr / col and the fp32 tier")
-    ctx.has_tfeat, ctx.has_live = tfeat is not None, slot_live is not None
-    # x_1 .. x_{L-1}, ymask, xs0, x0bits, h_seq, gates: saved, never differentiated
-    ctx.mark_non_differentiable(*output[:L - 1], *output[L:])
-    ctx.set_materialize_grads(False)
-    ctx.save_for_backward(*output[:L], output[L], output[L + 1], output[L + 2], output[L + 3], output[L + 4],
-                          residual, tfeat if tfeat is not None else residual, w_ih, w_hh, proj_weight, node_bias,
-                          *weights, sensor_slot, sensor_idx, slot_live if slot_live is not None else sensor_slot,
-                          nodetab_t, pairs_t, pos_slot_t, *((rowptr, col) if ctx.w_grad else ()))
+    ctx.kw = dict(p=a["p"], bf16=bf16)
+    # the arguments of encoder_trunk_backward by name (xs: xs0, then x_1 .. x_L)
+    _save_named(ctx, xs=f.xs, ymask=f.ymask, x0bits=f.x0bits, h_seq=f.h_seq, gates=f.gates,
+                rowptr=a["rowptr"] if ctx.w_grad else None, col=a["col"] if ctx.w_grad else None,
+                **{k: a[k] for k in ("residual", "tfeat", "w_ih", "w_hh", "proj_weight", "node_bias", "weights",
+                                     "sensor_slot", "sensor_idx", "slot_live", "nodetab_t", "pairs_t", "pos_slot_t")})
 
 
 def _et_bwd(ctx, grads):
-    L = ctx.L
-    g = grads[L - 1]
+    g = grads[ctx.h]
     if g is None:
-        return (None,) * ctx.n_in
-    sv = ctx.saved_tensors
-    xl = list(sv[:L])
-    ymask, xs0, x0bits, h_seq, gates = sv[L:L + 5]
-    residual, tfeat, w_ih, w_hh, proj_weight, node_bias = sv[L + 5:L + 11]
-    weights = list(sv[L + 11:2 * L + 11])
-    sensor_slot, sensor_idx, live, nodetab_t, pairs_t, pos_slot_t = sv[2 * L + 11:2 * L + 17]
-    rowptr, col = sv[2 * L + 17:] if ctx.w_grad else (None, None)
-    out = torch.ops.leakgnn.encoder_trunk_backward(
-        g, [xs0] + xl, ymask, x0bits, residual, tfeat if ctx.has_tfeat else None, w_ih, w_hh, h_seq, gates,
-        proj_weight, node_bias, weights, sensor_slot, sensor_idx, live if ctx.has_live else None, nodetab_t, pairs_t,
-        pos_slot_t, ctx.p, rowptr, col, bf16=ctx.bf16)
-    dw_ih, dw_hh, db_ih, db_hh, dWp, dbp = out[:6]
-    dWs, dbs = list(out[6:6 + L]), list(out[6 + L:6 + 2 * L])
-    return ((None, None, dw_ih, dw_hh, db_ih, db_hh, dWp, dbp, dWs, dbs) + (None,) * 13
-            + (out[6 + 2 * L] if ctx.w_grad else None, None, None))[:ctx.n_in]
+        return _named_grads(encoder_trunk, ctx.n_in)
+    out = torch.ops.leakgnn.encoder_trunk_backward(g, **_saved_named(ctx), **ctx.kw)
+    L = (len(out) - 7) // 2
+    (dw_ih, dw_hh, db_ih, db_hh, dWp, dbp), dWs, dbs, (dw,) = _split(out, 6, L, L, 1)
+    return _named_grads(encoder_trunk, ctx.n_in, w_ih=dw_ih, w_hh=dw_hh, b_ih=db_ih, b_hh=db_hh, proj_weight=dWp,
+                        node_bias=dbp, weights=dWs, biases=dbs, edge_w=dw if ctx.w_grad else None)
 
 
 encoder_trunk.register_autograd(_et_bwd, setup_context=_et_setup)

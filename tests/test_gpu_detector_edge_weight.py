@@ -416,3 +416,45 @@ def test_opcheck_trunk_ops_with_edge_w(B):
     _check(torch.ops.leakgnn.encoder_trunk.default,
            (r, tf, *gw, Wn, nb, wts, bs, slot, sidx, live, g.nodetab, g.pairs, g.nodetab_t, g.pairs_t, mk.nodetab_s,
             mk.pairs_s, mk.pos_slot_t, 0.1, seed, True, edge_w, g.rowptr, g.col), {"bf16": False})
+
+
+def test_encoder_trunk_edge_w_with_and_without_the_csr():
+    """encoder_trunk at B = 16, dropout 0.1, one CPU seed: edge_w, rowptr and col given, defaulted
+    from the right one by one, or all left out.  The autograd edge is an anchor only, so the output
+    and every parameter gradient are bit-identical in all of them (the bar of
+    test_learned_weights_fused_equals_separate_ops), and the backward returns as many gradients as
+    autograd saw arguments (autograd checks the count).  dL/dedge_w, where asked for, is non-zero
+    and reproducible; asking for it without the CSR is refused."""
+    m = _detector(_random_ref(41), _log_w(), True)
+    g, inc, slot, sidx, live, nons = m._device_state(DEV)
+    B, seed = 16, torch.tensor([12345], dtype=torch.long)
+    gen = torch.Generator().manual_seed(5)
+    r, tf = torch.randn(B, 36, 29, generator=gen).to(DEV), torch.randn(B, 36, 9, generator=gen).to(DEV)
+    up = torch.randn(661, B, 64, generator=gen).to(DEV)
+    gru = m.sensor_encoder.gru
+    mk = m._x0marks(g, slot)
+    leaves = lambda: [t.detach().clone().requires_grad_(True) for t in (  # noqa: E731
+        gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0, m.sensor_to_node.weight,
+        m.sensor_to_node.bias, *(c.lin.weight for c in m.convs), *(c.bias for c in m.convs))]
+    nl = len(m.convs)
+
+    def run(*tail):
+        p = leaves()
+        out = torch.ops.leakgnn.encoder_trunk(r, tf, *p[:6], p[6:6 + nl], p[6 + nl:], slot, sidx, live, g.nodetab,
+                                              g.pairs, g.nodetab_t, g.pairs_t, mk.nodetab_s, mk.pairs_s, mk.pos_slot_t,
+                                              0.1, seed, True, *tail)
+        out[nl - 1].backward(up)
+        return [o.detach() for o in out], [t.grad for t in p]
+
+    fixed, learn = g.w.detach().clone(), g.w.detach().clone().requires_grad_(True)
+    base = run()
+    for tail in ((fixed,), (fixed, g.rowptr), (fixed, g.rowptr, g.col), (learn, g.rowptr, g.col)):
+        outs, grads = run(*tail)
+        assert all(torch.equal(a, b) for a, b in zip(outs, base[0])), len(tail)
+        assert all(a is not None and torch.equal(a, b) for a, b in zip(grads, base[1])), len(tail)
+    assert fixed.grad is None and learn.grad is not None and float(learn.grad.abs().max()) > 0
+    again = g.w.detach().clone().requires_grad_(True)
+    run(again, g.rowptr, g.col)
+    assert torch.equal(again.grad, learn.grad)
+    with pytest.raises(NotImplementedError, match="needs rowptr / col"):
+        run(g.w.detach().clone().requires_grad_(True))

@@ -397,6 +397,24 @@ def test_norm_train_mode_on_the_kernels_masks():
     assert_grads_match_truth(got, g32, g64, ref32=g32d, rtol_tensor=5e-5)
 
 
+@pytest.mark.parametrize("B", [3, 16])
+def test_norm_train_mode_with_learned_edge_weights(B):
+    """Train mode, p = 0.1, 3 layers, learned edge weights, one fixed seed; B = 3 (fewer windows than
+    a tile) and 16: dropout's rescale and the edge-weight gradient together (every layer's
+    lg_sddmm_nm on the carried gradient, xn_l and the layer's own bits, scaled by 1 / (1 - p)).
+    The bars of test_norm_train_mode_on_the_kernels_masks and test_norm_with_learned_edge_weights_grad."""
+    from models import library
+    orig = _fixed_seed(987654321)
+    try:
+        m, lg, (o32, *_), (got, g32, g64, g32d) = _parity(B, 3, log_w=_log_w(0.1), learned=True, train_p=0.1)
+    finally:
+        library.seed_tensor = orig
+    assert float(got[LW].abs().max()) > 0
+    assert_close(lg, o32, what="train-mode logits, learned weights")
+    assert_grads_match_truth({LW: got[LW]}, {LW: g32[LW]}, {LW: g64[LW]}, ref32={LW: g32d[LW]})
+    assert_grads_match_truth(got, g32, g64, ref32=g32d, rtol_tensor=5e-5)
+
+
 def test_norm_none_is_the_skip_model():
     """LeakDetector(skip="residual", norm="none") gives logits torch.equal to
     LeakDetector(skip="residual"); norm="layer" with the same weights moves them by far more than RTOL."""

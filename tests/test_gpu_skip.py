@@ -253,16 +253,18 @@ def _skip_masks(m, B):
     return masks
 
 
-def _parity(B, layers, log_w=None, learned=False):
+def _parity(B, layers, log_w=None, learned=False, skip="residual"):
     sd = _random_sd(layers)
     r, tf, lab = _batch(B)
     _, _, pre64, up = _oracle(sd, r, tf, torch.float64, "cpu", layers, lab=lab, log_w=log_w)
     kw = dict(edge_weight=log_w.exp(), learn_edge_weight=learned) if log_w is not None else {}
-    m = _detector(sd, layers, **kw)
+    m = _detector(sd, layers, skip=skip, **kw)
     m.capture = {}
     lg = m(r.to(DEV), tf.to(DEV))
     lg.backward(up.float().to(DEV))
-    masks = _skip_masks(m, B)
+    # (a plain model keeps no fmask: without layers hip_relu_masks alone names every kink)
+    masks = (_skip_masks(m, B) if skip == "residual" else
+             hip_relu_masks(m.capture, B, len(m.node_names), len(m.pipe_ids), m.pipe_ends))
     ties = check_relu_ties(pre64, masks)
     o64, g64, _, _ = _oracle(sd, r, tf, torch.float64, "cpu", layers, up=up, masks=masks, log_w=log_w)
     o32, g32, _, _ = _oracle(sd, r, tf, torch.float32, "cpu", layers, up=up, masks=masks, log_w=log_w)
@@ -304,6 +306,19 @@ def test_skip_detector_12_layers_vs_oracle():
     scale 6.9e-5), 4 kink ties."""
     m, lg, (o32, o64, e_gpu, e_ref, scale), (got, g32, g64, g32d) = _parity(20, 12)
     assert e_gpu <= max(4 * e_ref, RTOL * scale), (e_gpu, e_ref, scale)
+    assert_grads_match_truth(got, g32, g64, ref32=g32d, rtol_tensor=5e-5)
+
+
+@pytest.mark.parametrize("skip,B", [("residual", 3), ("residual", 16), ("none", 3), ("none", 16)])
+def test_no_layers_vs_oracle(skip, B):
+    """gnn_layers = 0: the heads read the node init, and gnn_trunk_backward applies the node init's
+    mask and sums the non-sensor rows' bias gradient itself (no layer-0 launch does).  Node-major
+    under the skip at both B and for the plain model at B = 16, window-major for the plain model
+    at B = 3.  Without layers the skip oracle is the plain oracle.  The bars of
+    test_skip_detector_vs_oracle."""
+    m, lg, (o32, *_), (got, g32, g64, g32d) = _parity(B, 0, skip=skip)
+    assert len(m.convs) == 0 and m.capture["node_major"] == (skip == "residual" or B >= 16)
+    assert_close(lg, o32, what=f"L=0 skip={skip} B={B} logits")
     assert_grads_match_truth(got, g32, g64, ref32=g32d, rtol_tensor=5e-5)
 
 
