@@ -158,15 +158,18 @@ __device__ __forceinline__ uint32_t lg_row16_max_bits(uint32_t m) {
 // are uniform along K as the MFMA needs: W1 per wave (its own rows), the features per pipe
 // row (the B operand's columns; the row's 16 gather lanes take the max through DPP), so
 // hid = acc 2^-(sW + s_row) + b1 exactly unscaled.
-template <int D, bool BF, bool F16 = false>
+template <int D, Xf XF>
 __global__ void __launch_bounds__(NT)
-__attribute__((amdgpu_waves_per_eu((BF ? EG<D>::FWD_WG_PER_CU_BF : EG<D>::FWD_WG_PER_CU) * 2, F16 ? 2 : 4)))
+__attribute__((amdgpu_waves_per_eu((XF == Xf::Bf16 ? EG<D>::FWD_WG_PER_CU_BF : EG<D>::FWD_WG_PER_CU) * 2,
+                                   XF == Xf::F16x2 ? 2 : 4)))
 k_edge_fwd(const int64_t* __restrict__ ends, const float* __restrict__ h, const float* __restrict__ W1,
            const float* __restrict__ b1, const float* __restrict__ W2, const float* __restrict__ b2,
            float* __restrict__ logit, int64_t ldo, float* __restrict__ hid_out, uint32_t sb, uint32_t sn,
            lg_fastdiv fdP, int64_t BP, int64_t ntiles, int dropout, float p_drop, float dscale, uint64_t seed,
            uint32_t salt) {
     using G = EG<D>;
+    static constexpr bool BF = XF == Xf::Bf16, F16 = XF == Xf::F16x2;
+    static_assert(XF != Xf::F32, "no exact-fp32 form");
     constexpr int RBF = G::RB / 2;  // row blocks per wave
 #ifdef LG_KERNEL_LAB
     // kernel-lab builds only (results WRONG when set): 1 skip MFMA, 2 skip row loads, 4 skip split
@@ -550,14 +553,15 @@ __device__ __forceinline__ void edge_stream_zero(const EdgeScatter& sc, const fl
 //     tile = min over its rows of sf(row) + sg(row) (sf from the row's max |feature|), so every
 //     row's products carry 2^T and the tile's dW1 block is added times 2^-T.  T is reduced
 //     (LDS atomic min) from the tile's loaded rows before the previous tile's second barrier.
-template <int D, bool BF, int MODE = 0, bool F16 = false>
+template <int D, Xf XF, int MODE>
 __global__ void __launch_bounds__(NT)
 k_edge_bwd(const int64_t* __restrict__ ends, const float* __restrict__ h, const float* __restrict__ W1,
            const float* __restrict__ W2, const float* __restrict__ hid, const float* __restrict__ dlogit, int64_t ldo,
            float* __restrict__ dpipe, float* __restrict__ slab, double* __restrict__ db2slab, uint32_t sb,
            uint32_t sn, lg_fastdiv fdP, int64_t BP, int64_t ntiles, float dscale, EdgeScatter sc) {
     using G = EG<D>;
-    static_assert(!(F16 && BF), "one transform");
+    static constexpr bool BF = XF == Xf::Bf16, F16 = XF == Xf::F16x2;
+    static_assert(XF != Xf::F32, "no exact-fp32 form");
     constexpr bool SCAT = MODE == 1, STREAM = MODE == 2, WIN = MODE != 0;  // WIN: workgroups own windows
     constexpr int SL = (HID * G::K3 + 2 * HID + 1 + 3) & ~3;  // rows padded to 16 bytes (the reduce's vector loads)
     constexpr int NPL = F16 ? 2 : 3;  // image planes
@@ -1129,11 +1133,8 @@ inline int kEdgeLab(int) { return 0; }
 #endif
 
 // STREAM dynamic LDS: the images, the dfeat rows, two event blocks, the open nodes' sums
-// the backward's transform: the f16x2 split on the fp32 tier unless LG_F_BF16X3 asks for the
-// 3-way bf16 split; LG_F_BF16: one bf16 product
-bool edge_bwd_f16(int flags) { return !(flags & LG_F_BF16) && !(flags & LG_F_BF16X3); }
 int64_t edge_bwd_base_lds(int64_t D, int flags) {
-    const bool f16 = edge_bwd_f16(flags);
+    const bool f16 = lg_xf(flags) == Xf::F16x2;
     return D == 64 ? EG<64>::bwd_lds(f16) : EG<32>::bwd_lds(f16);
 }
 int64_t edge_stream_lds(int64_t D, int flags, const EdgeScatter& sc) {
@@ -1170,8 +1171,8 @@ extern "C" int lg_edge_head_fwd(const int64_t* ends, const float* h, const float
     const int64_t sb = nm ? 1 : N, sn = nm ? B : 1;
     const int64_t ntiles = cdiv(BP, tile_rows(D));
     // persistent grid sized to residency (tiles are dealt statically)
-    const bool bf = (flags & LG_F_BF16) != 0;
-    const int64_t per_cu = bf ? (D == 64 ? EG<64>::FWD_WG_PER_CU_BF : EG<32>::FWD_WG_PER_CU_BF)
+    const Xf xf = lg_xf(flags);
+    const int64_t per_cu = xf == Xf::Bf16 ?(D == 64 ? EG<64>::FWD_WG_PER_CU_BF : EG<32>::FWD_WG_PER_CU_BF)
                               : (D == 64 ? EG<64>::FWD_WG_PER_CU : EG<32>::FWD_WG_PER_CU);
     const unsigned grid = static_cast<unsigned>(std::min<int64_t>(ntiles, per_cu * lg_num_cus()));
     const float scale = dropout ? 1.0f / (1.0f - dropout_p) : 1.0f;
@@ -1181,20 +1182,19 @@ extern "C" int lg_edge_head_fwd(const int64_t* ends, const float* h, const float
 #else
     const int dropout_arg = dropout;
 #endif
-#define LG_EDGE_FWD(DD, BFB, F16B)                                                                                \
+#define LG_EDGE_FWD(DD, XF)                                                                                       \
     do {                                                                                                          \
-        if (!allow_lds(k_edge_fwd<DD, BFB, F16B>, EG<DD>::FWD_LDS)) return LG_EHIP;                               \
-        lg_launch(k_edge_fwd<DD, BFB, F16B>, grid, NT, EG<DD>::FWD_LDS, s, ends, h, w1, b1, w2, b2, logits, ldo, hid,  \
+        if (!allow_lds(k_edge_fwd<DD, XF>, EG<DD>::FWD_LDS)) return LG_EHIP;                                      \
+        lg_launch(k_edge_fwd<DD, XF>, grid, NT, EG<DD>::FWD_LDS, s, ends, h, w1, b1, w2, b2, logits, ldo, hid,    \
                   sb, sn, fdP, BP, ntiles, dropout_arg, dropout_p, scale, seed, salt);                            \
     } while (0)
-    // fp32 tier at D = 64: the f16x2 transform unless LG_F_BF16X3 asks for the 3-way bf16 split
-    const bool f16 = !bf && !(flags & LG_F_BF16X3);
+    // the f16x2 form exists at D = 64 only: the fp32 tier at D = 32 runs on the 3-way bf16 split
     if (D == 64) {
-        if (bf) LG_EDGE_FWD(64, true, false);
-        else if (f16) LG_EDGE_FWD(64, false, true);
-        else LG_EDGE_FWD(64, false, false);
+        if (xf == Xf::Bf16) LG_EDGE_FWD(64, Xf::Bf16);
+        else if (xf == Xf::F16x2) LG_EDGE_FWD(64, Xf::F16x2);
+        else LG_EDGE_FWD(64, Xf::Bf16x3);
     } else {
-        if (bf) LG_EDGE_FWD(32, true, false); else LG_EDGE_FWD(32, false, false);
+        if (xf == Xf::Bf16) LG_EDGE_FWD(32, Xf::Bf16); else LG_EDGE_FWD(32, Xf::Bf16x3);
     }
 #undef LG_EDGE_FWD
     LG_RET_IF_LAUNCH_FAILED();
@@ -1249,34 +1249,34 @@ int edge_bwd_impl(const int64_t* ends, const float* h, const float* w1, const fl
         if (hipMemsetAsync(slab, 0, SL * grid * sizeof(float), s) != hipSuccess) return LG_EHIP;
         if (hipMemsetAsync(dslab, 0, grid * sizeof(double), s) != hipSuccess) return LG_EHIP;
     } else {
-        const bool bf = (flags & LG_F_BF16) != 0, f16 = edge_bwd_f16(flags);
+        const Xf xf = lg_xf(flags);
         const bool stream = scat && scat->spipe;
         const int64_t base = edge_bwd_base_lds(D, flags);
         const int64_t lds = stream ? edge_stream_lds(D, flags, *scat) : scat ? base + 4 * (N + 1 + 2 * P) : base;
-#define LG_EDGE_BWD(DD, BFB, F16B)                                                                                \
+#define LG_EDGE_BWD(DD, XF)                                                                                       \
     do {                                                                                                          \
         if (stream) {                                                                                             \
-            if (!allow_lds(k_edge_bwd<DD, BFB, 2, F16B>, lds)) return LG_EHIP;                                     \
-            lg_launch(k_edge_bwd<DD, BFB, 2, F16B>, grid, NT, lds, s, ends, h, w1, w2, hid, dlogits, ldo, dpipe,    \
-                      slab, dslab, sb, sn, fdP, BP, ntiles, scale, *scat);                                         \
+            if (!allow_lds(k_edge_bwd<DD, XF, 2>, lds)) return LG_EHIP;                                           \
+            lg_launch(k_edge_bwd<DD, XF, 2>, grid, NT, lds, s, ends, h, w1, w2, hid, dlogits, ldo, dpipe, slab,   \
+                      dslab, sb, sn, fdP, BP, ntiles, scale, *scat);                                              \
         } else if (scat) {                                                                                        \
-            if (!allow_lds(k_edge_bwd<DD, BFB, 1, F16B>, lds)) return LG_EHIP;                                     \
-            lg_launch(k_edge_bwd<DD, BFB, 1, F16B>, grid, NT, lds, s, ends, h, w1, w2, hid, dlogits, ldo, dpipe,    \
-                      slab, dslab, sb, sn, fdP, BP, ntiles, scale, *scat);                                         \
+            if (!allow_lds(k_edge_bwd<DD, XF, 1>, lds)) return LG_EHIP;                                           \
+            lg_launch(k_edge_bwd<DD, XF, 1>, grid, NT, lds, s, ends, h, w1, w2, hid, dlogits, ldo, dpipe, slab,   \
+                      dslab, sb, sn, fdP, BP, ntiles, scale, *scat);                                              \
         } else {                                                                                                  \
-            if (!allow_lds(k_edge_bwd<DD, BFB, 0, F16B>, lds)) return LG_EHIP;                                     \
-            lg_launch(k_edge_bwd<DD, BFB, 0, F16B>, grid, NT, lds, s, ends, h, w1, w2, hid, dlogits, ldo, dpipe,    \
-                      slab, dslab, sb, sn, fdP, BP, ntiles, scale, none);                                          \
+            if (!allow_lds(k_edge_bwd<DD, XF, 0>, lds)) return LG_EHIP;                                           \
+            lg_launch(k_edge_bwd<DD, XF, 0>, grid, NT, lds, s, ends, h, w1, w2, hid, dlogits, ldo, dpipe, slab,   \
+                      dslab, sb, sn, fdP, BP, ntiles, scale, none);                                               \
         }                                                                                                         \
     } while (0)
         if (D == 64) {
-            if (bf) LG_EDGE_BWD(64, true, false);
-            else if (f16) LG_EDGE_BWD(64, false, true);
-            else LG_EDGE_BWD(64, false, false);
+            if (xf == Xf::Bf16) LG_EDGE_BWD(64, Xf::Bf16);
+            else if (xf == Xf::F16x2) LG_EDGE_BWD(64, Xf::F16x2);
+            else LG_EDGE_BWD(64, Xf::Bf16x3);
         } else {
-            if (bf) LG_EDGE_BWD(32, true, false);
-            else if (f16) LG_EDGE_BWD(32, false, true);
-            else LG_EDGE_BWD(32, false, false);
+            if (xf == Xf::Bf16) LG_EDGE_BWD(32, Xf::Bf16);
+            else if (xf == Xf::F16x2) LG_EDGE_BWD(32, Xf::F16x2);
+            else LG_EDGE_BWD(32, Xf::Bf16x3);
         }
 #undef LG_EDGE_BWD
     }

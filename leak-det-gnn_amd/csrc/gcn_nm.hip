@@ -25,6 +25,7 @@
 // Tiles are ordered window-group-major and dealt XCD-aware.
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 #include "common.h"
 #include "reduce.h"
 #include "split_bf16.h"
@@ -186,13 +187,25 @@ constexpr uint32_t kNm3RowOob = 0x80000000u;
 constexpr uint32_t kNm3BlkOob = 0x7FFFF000u;
 constexpr uint64_t kNm3MaxBytes = 0x7FFFF000u;
 
-// BF (LG_F_BF16, the bf16 node-MLP tier): the transform's single hi x hi product.
-template <int D, bool DROP, bool RELU, bool SPLIT, int WAVES, bool BF = false>
+// The variants of the three trunk kernels: template <int D, Xf XF, unsigned OPT>, OPT a set of
+// the bits below.  Which (D, XF, OPT) exist is the *_has predicate next to each kernel.  A body
+// names its bits as `static constexpr bool`: a name for a template argument with no stack slot,
+// so a variant's code does not depend on how many names its body declares.
+constexpr unsigned kFwdDrop = 1, kFwdRelu = 2, kFwdX0 = 4, kFwdSkip = 8, kFwdOpts = 16;
+constexpr unsigned kBwdMaskIn = 1, kBwdNb = 2, kBwdMb = 4, kBwdX0 = 8, kBwdSkip = 16, kBwdOpts = 32;
+
+// XF: Bf16x3, Bf16 (the split's single hi x hi product) or F32 (no split: exact fp32 MFMA)
+constexpr bool nm3_has(Xf xf, unsigned opt) { return xf != Xf::F16x2 && !(opt & ~(kFwdDrop | kFwdRelu)); }
+
+template <int D, Xf XF, unsigned OPT, int WAVES>
 __global__ void __launch_bounds__(64 * WAVES, WAVES >= 5 ? 4 : 1)
 k_gcn_fwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, const float* __restrict__ x,
               const float* __restrict__ W, const float* __restrict__ bias, float* __restrict__ y, uint32_t N,
               uint32_t B, uint32_t ngroups, lg_fastdiv fdN, float p_drop, float dscale, uint64_t seed,
               uint32_t salt, uint16_t* __restrict__ ymask) {
+    static_assert(nm3_has(XF, OPT), "not a variant of this kernel");
+    static constexpr bool DROP = OPT & kFwdDrop, RELU = OPT & kFwdRelu;
+    static constexpr bool SPLIT = XF != Xf::F32, BF = XF == Xf::Bf16;
     using G = NmGeo<D>;
     using LY = Nm3Lds<D, SPLIT, WAVES>;
     constexpr int SB = LY::SB;
@@ -636,7 +649,14 @@ struct PcX0 {
 // the producers gathered a moment ago) with the compiler's loads -- outside the producers'
 // prefetch registers and vmcnt counts --, takes the mask bits from f and adds x as the last
 // fp32 operation before the store.
-template <int D, bool DROP, bool RELU, bool BF, bool F16, int kPcProd, int NC, bool X0 = false, bool SKIP = false>
+// The variants: DROP x RELU of the dense layer and of X0 on every transform but F32, and of SKIP
+// on the dense fp32-tier layers.
+constexpr bool pc_has(Xf xf, unsigned opt) {
+    if (xf == Xf::F32 || opt >= kFwdOpts) return false;
+    return !(opt & kFwdSkip) || (!(opt & kFwdX0) && xf != Xf::Bf16);
+}
+
+template <int D, Xf XF, unsigned OPT, int kPcProd, int NC>
 __global__ void __launch_bounds__(64 * kPcProd * (1 + NC), kPcProd * (1 + NC) / 4)
 k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, const float* __restrict__ x,
              const float* __restrict__ W, const float* __restrict__ bias, float* __restrict__ y, uint32_t N,
@@ -644,14 +664,16 @@ k_gcn_fwd_pc(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, co
              uint32_t salt, uint16_t* __restrict__ ymask, PcX0 x0) {
     using G = NmGeo<D>;
     using LY = PcLds<D, kPcProd, NC>;
+    static constexpr bool DROP = OPT & kFwdDrop, RELU = OPT & kFwdRelu, X0 = OPT & kFwdX0, SKIP = OPT & kFwdSkip;
+    static constexpr bool BF = XF == Xf::Bf16, F16 = XF == Xf::F16x2;
+    static_assert(pc_has(XF, OPT), "not a variant of this kernel");
+    static_assert(!SKIP || (!X0 && !BF), "the skip lives on the dense fp32-tier layers");
     constexpr int NPF = X0 ? LG_PC_NPF_X0 : LG_PC_NPF;
     static_assert(NPF >= 1 && NPF <= kLgNmInline, "prefetch depth");
     constexpr int KS = D / 32;
     constexpr int NP = BF ? 1 : 3;
     constexpr int R = kPcRing;
     constexpr int NT = 64 * kPcProd * (1 + NC);
-    static_assert(!(BF && F16), "one transform");
-    static_assert(!SKIP || (!X0 && !BF), "the skip lives on the dense fp32-tier layers");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* lds = reinterpret_cast<float*>(smem);
     float* wst = lds + LY::WOFF;
@@ -1364,14 +1386,25 @@ struct NbX0 {
 // dy rows are added where the dx tile comes back from LDS in the row layout, one fp32 add per
 // element after the product; the input mask (mask_out) and the node-bias sum then act on the
 // summed dx, in that layout too (the x tile is still in LDS).
-template <int D, bool MASK_IN, bool NB, bool BF = false, bool MB = false, bool X0 = false, bool F16 = false,
-          bool SKIP = false>
+// The variants: with and without NB, on every transform but F32, of the four input forms (plain,
+// X0, MASK_IN from y, MASK_IN from bits); SKIP on the last one, fp32 tier.
+constexpr bool nb3_has(Xf xf, unsigned opt) {
+    const bool mask_in = opt & kBwdMaskIn, mb = opt & kBwdMb, x0 = opt & kBwdX0, skip = opt & kBwdSkip;
+    if (xf == Xf::F32 || opt >= kBwdOpts || (mb && !mask_in) || (x0 && mask_in)) return false;
+    return !skip || (mb && xf != Xf::Bf16);
+}
+
+template <int D, Xf XF, unsigned OPT>
 __global__ void __launch_bounds__(64 * kNmBwdWaves3, 2)
 k_gcn_bwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, const float* __restrict__ dy,
               const float* __restrict__ yv, const float* __restrict__ x, const float* __restrict__ W,
               const int32_t* __restrict__ node_slot, float* __restrict__ dxo, float* __restrict__ slab, uint32_t N,
               uint32_t B, uint32_t ngroups, lg_fastdiv fdN, int mask_out, float scale_in, float scale_out,
               const uint16_t* __restrict__ ymask, NbX0 x0) {
+    static constexpr bool MASK_IN = OPT & kBwdMaskIn, NB = OPT & kBwdNb, MB = OPT & kBwdMb, X0 = OPT & kBwdX0,
+                          SKIP = OPT & kBwdSkip;
+    static constexpr bool BF = XF == Xf::Bf16, F16 = XF == Xf::F16x2;
+    static_assert(nb3_has(XF, OPT), "not a variant of this kernel");
     static_assert(!MB || MASK_IN, "mask bits replace the y gather of MASK_IN");
     static_assert(!SKIP || (MB && !X0 && !BF), "the skip reads its branch mask as bits, dense fp32 tier");
     constexpr bool MY = MASK_IN && !MB;  // mask from gathered y rows
@@ -1535,7 +1568,6 @@ k_gcn_bwd_nm3(const int32_t* __restrict__ tab, const int2* __restrict__ pairs, c
     // the record)
     auto pslot_of = [&](uint32_t i) -> int { return X0 ? __builtin_amdgcn_readfirstlane(x0.pos_slot[i]) : -1; };
     // W^T split to LDS: element (o, i) of W lands at row i, column o of each part
-    static_assert(!(F16 && BF), "one transform");
     int sW = 0;  // F16: W's scale exponent (every wave reads all of W for its max: no barrier)
     if constexpr (F16) {
         uint32_t m = 0;
@@ -2367,21 +2399,28 @@ int nm_grid(Kern kernel, int threads, size_t dyn, int64_t ntiles, int waves, int
 
 bool nm_fits(int64_t B, int64_t N, int64_t D) { return N * B * D * 4 <= static_cast<int64_t>(kNm3MaxBytes); }
 
-template <int D, bool DR, bool RL>
-auto nm3_kernel(int flags) {
-    if (flags & LG_F_BF16) return k_gcn_fwd_nm3<D, DR, RL, true, 4, true>;
-    return (flags & LG_F_F32_MFMA) ? k_gcn_fwd_nm3<D, DR, RL, false, 4> : k_gcn_fwd_nm3<D, DR, RL, true, 4>;
+// Runtime values -> compile-time constants.  with_const calls f(std::integral_constant<V>{}) for
+// the V of the list equal to v; nm_dispatch does so for D, the transform and the option bits
+// (opt < NOPT) at once.  f returns whether it launched; it names a kernel only behind
+// `if constexpr (<kernel>_has(XF, OPT))`, so those predicates are the list of what is compiled.
+template <auto... Vs>
+struct Vals {};
+template <unsigned... Is>
+constexpr Vals<Is...> vals_upto(std::integer_sequence<unsigned, Is...>) {
+    return {};
 }
-template <int D, bool DR, bool RL>
-auto pc_skip_kernel(bool f16) {
-    return f16 ? k_gcn_fwd_pc<D, DR, RL, false, true, kPcProdN, kPcNC, false, true>
-               : k_gcn_fwd_pc<D, DR, RL, false, false, kPcProdN, kPcNC, false, true>;
+template <auto... Vs, typename T, typename F>
+bool with_const(Vals<Vs...>, T v, F&& f) {
+    return ((v == Vs && f(std::integral_constant<decltype(Vs), Vs>{})) || ...);
 }
-template <int D, bool DR, bool RL, bool X0>
-auto pc_kernel(bool bf16, bool f16) {
-    return bf16 ? k_gcn_fwd_pc<D, DR, RL, true, false, kPcProdN, kPcNC, X0>
-                : (f16 ? k_gcn_fwd_pc<D, DR, RL, false, true, kPcProdN, kPcNC, X0>
-                       : k_gcn_fwd_pc<D, DR, RL, false, false, kPcProdN, kPcNC, X0>);
+template <unsigned NOPT, typename F>
+bool nm_dispatch(int64_t D, Xf xf, unsigned opt, F&& f) {
+    return with_const(Vals<32, 64>{}, D, [&](auto d) {
+        return with_const(Vals<Xf::Bf16, Xf::F16x2, Xf::Bf16x3, Xf::F32>{}, xf, [&](auto x) {
+            return with_const(vals_upto(std::make_integer_sequence<unsigned, NOPT>{}), opt,
+                              [&](auto o) { return f(d, x, o); });
+        });
+    });
 }
 
 // lg_gcn_fwd_nm_bits (x0 == NULL), lg_gcn_fwd_nm_x0 (x the sensor rows, *x0 the rest) and
@@ -2401,8 +2440,6 @@ int nm_fwd(const int32_t* nodetab, const int32_t* pairs, const float* x, const f
     const int64_t ngroups = (B + 15) / 16, ntiles = ngroups * N;
     const float scale = drop ? 1.0f / (1.0f - dropout_p) : 1.0f;
     const float* bp = (flags & LG_F_BIAS) ? bias : nullptr;
-    const bool relu = (flags & LG_F_RELU) != 0;
-    const bool bf16 = (flags & LG_F_BF16) != 0;
     // Kernel and transform (results: see include/leakgnn.h):
     //   fp32 tier, default: the producer / consumer pipeline k_gcn_fwd_pc with the 2-way fp16
     //     transform; LG_F_BF16X3: the same pipeline on the 3-way bf16 split;
@@ -2410,50 +2447,44 @@ int nm_fwd(const int32_t* nodetab, const int32_t* pairs, const float* x, const f
     //     fp32 MFMA, bit-identical to lg_gcn_fwd);
     //   bf16 tier (LG_F_BF16): nm3's single bf16 product, or pc's with LG_F_PC.
     // The compressed layer-0 input runs on pc only.
-    const bool nm3 = !x0 && ((flags & (LG_F_NM3 | LG_F_F32_MFMA)) != 0 || (bf16 && !(flags & LG_F_PC)));
-    const bool f16 = !bf16 && !(flags & LG_F_BF16X3);
+    const bool nm3 =
+        !x0 && ((flags & (LG_F_NM3 | LG_F_F32_MFMA)) != 0 || ((flags & LG_F_BF16) && !(flags & LG_F_PC)));
+    const Xf xf = lg_xf(flags, nm3);
+    const unsigned opt = (drop ? kFwdDrop : 0u) | ((flags & LG_F_RELU) ? kFwdRelu : 0u) | (x0 ? kFwdX0 : 0u) |
+                         (skip ? kFwdSkip : 0u);
     const int2* pr = reinterpret_cast<const int2*>(pairs);
     const lg_fastdiv fd = lg_make_fastdiv(static_cast<uint32_t>(N));
     hipStream_t s = lg_stream(stream);
     const uint32_t N32 = static_cast<uint32_t>(N), B32 = static_cast<uint32_t>(B), G32 = static_cast<uint32_t>(ngroups);
     const PcX0 xz = x0 ? *x0 : PcX0{nullptr, nullptr, 1.f, 0u};
-    auto launch = [&](auto dc, auto drc) {
+    const bool launched = nm_dispatch<kFwdOpts>(D, xf, opt, [&](auto dc, auto xc, auto oc) {
         constexpr int DD = decltype(dc)::value;
-        constexpr bool DR = decltype(drc)::value;
-        if (skip) {
-            auto kern = relu ? pc_skip_kernel<DD, DR, true>(f16) : pc_skip_kernel<DD, DR, false>(f16);
-            const size_t dyn = PcLds<DD, kPcProdN, kPcNC>::BYTES;
-            const int thr = 64 * kPcProdN * (1 + kPcNC);
-            const int grid = nm_grid(kern, thr, dyn, ntiles, 4, 1);
-            lg_launch(kern, grid, thr, dyn, s, nodetab, pr, x, W, bp, y, N32, B32, G32, fd, dropout_p, scale, seed,
-                      salt, ymask, xz);
-        } else if (nm3) {
-            auto kern = relu ? nm3_kernel<DD, DR, true>(flags) : nm3_kernel<DD, DR, false>(flags);
-            const size_t dyn = (flags & LG_F_F32_MFMA) && !bf16 ? Nm3Lds<DD, false, 4>::BYTES : Nm3Lds<DD, true, 4>::BYTES;
-            const int grid = nm_grid(kern, 64 * 4, dyn, ntiles, 4, 3);
-            lg_launch(kern, grid, 64 * 4, dyn, s, nodetab, pr, x, W, bp, y, N32, B32, G32, fd, dropout_p, scale, seed,
-                      salt, ymask);
-        } else {
-            auto kern = x0 ? (relu ? pc_kernel<DD, DR, true, true>(bf16, f16) : pc_kernel<DD, DR, false, true>(bf16, f16))
-                           : (relu ? pc_kernel<DD, DR, true, false>(bf16, f16) : pc_kernel<DD, DR, false, false>(bf16, f16));
-            const size_t dyn = PcLds<DD, kPcProdN, kPcNC>::BYTES;
-            const int thr = 64 * kPcProdN * (1 + kPcNC);
-            const int grid = nm_grid(kern, thr, dyn, ntiles, 4, 1);
-            lg_launch(kern, grid, thr, dyn, s, nodetab, pr, x, W, bp, y, N32, B32, G32, fd, dropout_p, scale, seed,
-                      salt, ymask, xz);
+        constexpr Xf XF = decltype(xc)::value;
+        constexpr unsigned OPT = decltype(oc)::value;
+        if constexpr (nm3_has(XF, OPT)) {
+            if (nm3) {
+                auto kern = k_gcn_fwd_nm3<DD, XF, OPT, 4>;
+                const size_t dyn = Nm3Lds<DD, XF != Xf::F32, 4>::BYTES;
+                const int grid = nm_grid(kern, 64 * 4, dyn, ntiles, 4, 3);
+                lg_launch(kern, grid, 64 * 4, dyn, s, nodetab, pr, x, W, bp, y, N32, B32, G32, fd, dropout_p, scale,
+                          seed, salt, ymask);
+                return true;
+            }
         }
-    };
-    using I32 = std::integral_constant<int, 32>;
-    using I64 = std::integral_constant<int, 64>;
-    using T = std::true_type;
-    using F = std::false_type;
-    if (D == 64) {
-        if (drop) launch(I64{}, T{});
-        else launch(I64{}, F{});
-    } else {
-        if (drop) launch(I32{}, T{});
-        else launch(I32{}, F{});
-    }
+        if constexpr (pc_has(XF, OPT)) {
+            if (!nm3) {
+                auto kern = k_gcn_fwd_pc<DD, XF, OPT, kPcProdN, kPcNC>;
+                const size_t dyn = PcLds<DD, kPcProdN, kPcNC>::BYTES;
+                const int thr = 64 * kPcProdN * (1 + kPcNC);
+                const int grid = nm_grid(kern, thr, dyn, ntiles, 4, 1);
+                lg_launch(kern, grid, thr, dyn, s, nodetab, pr, x, W, bp, y, N32, B32, G32, fd, dropout_p, scale,
+                          seed, salt, ymask, xz);
+                return true;
+            }
+        }
+        return false;
+    });
+    if (!launched) return LG_EUNSUPPORTED;  // no such kernel: not reached by a combination that passed the checks
     LG_RET_IF_LAUNCH_FAILED();
     return LG_OK;
 }
@@ -2541,63 +2572,30 @@ int nm_bwd(const int32_t* nodetab_t, const int32_t* pairs_t, const float* dy, co
     if (ws_bytes < lg_gcn_bwd_nm_workspace_bytes(D)) return LG_EINVAL;
     float* slab = static_cast<float*>(workspace);
     hipStream_t s = lg_stream(stream);
-    const bool bf = (flags & LG_F_BF16) != 0;
-    // fp32 tier: the f16x2 transform unless LG_F_BF16X3 asks for the 3-way bf16 split
-    const bool f16 = !bf && !(flags & LG_F_BF16X3);
+    // LG_F_NM3 / LG_F_F32_MFMA are forward-only: the backward knows the three-way choice
+    const Xf xf = lg_xf(flags);
+    const unsigned opt = (mask_in ? kBwdMaskIn : 0u) | (node_slot ? kBwdNb : 0u) | (mbits ? kBwdMb : 0u) |
+                         (x0 ? kBwdX0 : 0u) | (skip ? kBwdSkip : 0u);
     const NbX0 xz = x0 ? *x0 : NbX0{nullptr, nullptr, 1.f, 0u, nullptr};
-    // k_gcn_bwd_nm3: the 3-way bf16 split (fp32 tier) or the single bf16 product (LG_F_BF16)
     int grid = 1;
     // B == 0 still runs one (empty) launch so the slab holds zeros
-    auto launch = [&](auto kern, size_t dyn3) {
-        grid = std::min<int>(nm_grid(kern, 64 * kNmBwdWaves3, dyn3, std::max<int64_t>(ntiles, 1), kNmBwdWaves3, 2),
-                             2 * lg_num_cus());
-        lg_launch(kern, grid, 64 * kNmBwdWaves3, dyn3, s, nodetab_t, pr, dy, y, x, W, node_slot, dx_out, slab,
-                  static_cast<uint32_t>(N), static_cast<uint32_t>(B), static_cast<uint32_t>(ngroups), fd, mask_out,
-                  scale_in, scale_out, ymask, xz);
-    };
-#define LG_NM_BWD_P(DD, MI, NBB, MBB, X0B)                                                                        \
-    launch(bf ? k_gcn_bwd_nm3<DD, MI, NBB, true, MBB, X0B>                                                        \
-              : (f16 ? k_gcn_bwd_nm3<DD, MI, NBB, false, MBB, X0B, true> : k_gcn_bwd_nm3<DD, MI, NBB, false, MBB, X0B>), \
-           Nb3Lds<DD, MI>::BYTES)
-#define LG_NM_BWD(DD, MI, NBB)                                                                                     \
-    do {                                                                                                           \
-        if constexpr (!MI) {                                                                                       \
-            if (x0) {                                                                                              \
-                LG_NM_BWD_P(DD, false, NBB, false, true);                                                          \
-                break;                                                                                             \
-            }                                                                                                      \
-        }                                                                                                          \
-        if (MI && mbits) LG_NM_BWD_P(DD, MI, NBB, MI, false);                                                      \
-        else LG_NM_BWD_P(DD, MI, NBB, false, false);                                                               \
-    } while (0)
-#define LG_NM_BWD_D(DD)                                  \
-    do {                                                 \
-        if (mask_in) {                                   \
-            if (node_slot) LG_NM_BWD(DD, true, true);    \
-            else LG_NM_BWD(DD, true, false);             \
-        } else {                                         \
-            if (node_slot) LG_NM_BWD(DD, false, true);   \
-            else LG_NM_BWD(DD, false, false);            \
-        }                                                \
-    } while (0)
-#define LG_NM_BWD_S(DD, NBB)                                                                     \
-    launch(f16 ? k_gcn_bwd_nm3<DD, true, NBB, false, true, false, true, true>                    \
-               : k_gcn_bwd_nm3<DD, true, NBB, false, true, false, false, true>,                  \
-           Nb3Lds<DD, true>::BYTES)
-    if (skip) {
-        if (D == 64) {
-            if (node_slot) LG_NM_BWD_S(64, true);
-            else LG_NM_BWD_S(64, false);
-        } else {
-            if (node_slot) LG_NM_BWD_S(32, true);
-            else LG_NM_BWD_S(32, false);
+    const bool launched = nm_dispatch<kBwdOpts>(D, xf, opt, [&](auto dc, auto xc, auto oc) {
+        constexpr int DD = decltype(dc)::value;
+        constexpr Xf XF = decltype(xc)::value;
+        constexpr unsigned OPT = decltype(oc)::value;
+        if constexpr (nb3_has(XF, OPT)) {
+            auto kern = k_gcn_bwd_nm3<DD, XF, OPT>;
+            const size_t dyn3 = Nb3Lds<DD, (OPT & kBwdMaskIn) != 0>::BYTES;
+            grid = std::min<int>(nm_grid(kern, 64 * kNmBwdWaves3, dyn3, std::max<int64_t>(ntiles, 1), kNmBwdWaves3, 2),
+                                 2 * lg_num_cus());
+            lg_launch(kern, grid, 64 * kNmBwdWaves3, dyn3, s, nodetab_t, pr, dy, y, x, W, node_slot, dx_out, slab,
+                      static_cast<uint32_t>(N), static_cast<uint32_t>(B), static_cast<uint32_t>(ngroups), fd, mask_out,
+                      scale_in, scale_out, ymask, xz);
+            return true;
         }
-    } else if (D == 64) LG_NM_BWD_D(64);
-    else LG_NM_BWD_D(32);
-#undef LG_NM_BWD_S
-#undef LG_NM_BWD_D
-#undef LG_NM_BWD
-#undef LG_NM_BWD_P
+        return false;
+    });
+    if (!launched) return LG_EUNSUPPORTED;  // no such kernel: not reached by a combination that passed the checks
     LG_RET_IF_LAUNCH_FAILED();
     const int64_t L = D * D + 2 * D;
     const LgSlabSeg segs[3] = {{0, D * D, dW}, {D * D, D, db}, {D * D + D, D, dnode_bias}};

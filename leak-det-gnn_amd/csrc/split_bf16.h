@@ -58,6 +58,23 @@ __device__ __forceinline__ void split3_x8(const f32x4& u, const f32x4& v, lg_bf1
 __device__ __forceinline__ f32x4 mfma_bf(const lg_bf16x8& a, const lg_bf16x8& b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
+// The numeric transform of a kernel's fp32 products on the MFMA units: a kernel is compiled
+// for exactly one (template <..., Xf XF, ...>).
+enum class Xf {
+    Bf16,    // LG_F_BF16, the bf16 node-MLP tier: the single hi x hi bf16 product
+    F16x2,   // the fp32 tier's default: the 2-way f16 split below (3 f16 MFMAs per product)
+    Bf16x3,  // LG_F_BF16X3: the 3-way bf16 split above (6 bf16 MFMAs per product)
+    F32,     // LG_F_F32_MFMA: exact fp32 MFMA (k_gcn_fwd_nm3 only)
+};
+// The one rule from a flags word to the transform.  nm3: for k_gcn_fwd_nm3, the kernel behind
+// LG_F_NM3 / LG_F_F32_MFMA, which has the exact fp32 form and no f16 one; every other kernel
+// knows the first three only.
+inline Xf lg_xf(int flags, bool nm3 = false) {
+    if (flags & LG_F_BF16) return Xf::Bf16;
+    if (nm3) return (flags & LG_F_F32_MFMA) ? Xf::F32 : Xf::Bf16x3;
+    return (flags & LG_F_BF16X3) ? Xf::Bf16x3 : Xf::F16x2;
+}
+
 // acc += a * b on split operands: the six terms with i + j <= 2, smallest first
 // BF (the bf16 node-MLP tier, LG_F_BF16): the single hi x hi product — operands rounded to
 // bf16, fp32 accumulate.  Unused split parts and their LDS reads are dead code then.
