@@ -655,6 +655,38 @@ int lg_layernorm_bwd(const float* dxn, const float* x, const float* stats, const
                      float* dx_out, float* dgamma, float* dbeta, int64_t rows, int64_t D, int flags, float scale_out,
                      void* workspace, int64_t ws_bytes, lg_stream_t stream);
 
+/* K-hop diffusion of the node init (APPNP's personalised-PageRank propagation; csrc/diffuse.hip;
+ * added to ABI 26 without a bump: additions only).  Node-major x0, z, g, dx0 : fp32 [N][B][D], D in
+ * {32, 64} (LG_EUNSUPPORTED otherwise).  Ahat comes from the node tables of lg_nm_table_build (records
+ * 0 .. N-1; self loop and edge weights included): nodetab / pairs forward, nodetab_t / pairs_t backward.
+ *   lg_diffuse_fwd:  z_0 = x0,  z_{k+1} = (1 - alpha) Ahat z_k + alpha x0,  z_out = z_hops
+ *   lg_diffuse_bwd:  u = g, acc = 0;  hops times: acc += alpha u, u = (1 - alpha) Ahat^T u;
+ *                    dx0 = u + acc;  dx0_out = LG_F_MASK_OUT ? dx0 * scale_out * [x0 > 0] : dx0
+ *                    (the node init's ReLU / dropout mask, the last arithmetic, as lg_layernorm_bwd's;
+ *                    x0 may be NULL without the flag, LG_EINVAL with it)
+ * Two forms of each pass, the same bits from both (a row's entries are summed in the record's CSR
+ * order, inline pairs then overflow pairs, with the same unfused fp32 operations):
+ *   resident: ONE launch runs every hop; a workgroup owns one window and a channel slice of 32, 16 or
+ *     8 floats whose N rows stay in LDS (lg_diffuse_slice(N, D): the widest slice whose rows fit the
+ *     160 KiB of LDS and 12 rows in each of 512 threads' registers, i.e. N <= 768, 1536, 3072; 0: none).  x0 is read once, z_out written
+ *     once.  No atomics, no cross-workgroup hand-off.  Needs no workspace.
+ *   hop-wise: one launch per hop, ping-pong between the output and the workspace, any N.  Taken when
+ *     no slice fits, or under LG_F_DIFFUSE_HOPWISE (tests, measurement).
+ * workspace: lg_diffuse_workspace_bytes(B, N, D, hops, flags, backward) bytes, 16-byte aligned (0 for
+ * the resident form and for hops == 1: NULL is then accepted); fewer is LG_EINVAL.
+ * LG_EINVAL: a NULL table, input or output, B < 0, N <= 0, hops outside 1 .. 64, alpha outside [0, 1]
+ * (NaN included), the output aliasing the input (x0 == z_out, g == dx0_out, x0 == dx0_out under the
+ * mask).  Other flags: LG_EUNSUPPORTED, as is N * B >= 2^31.  B == 0 returns LG_OK without a launch. */
+#define LG_F_DIFFUSE_HOPWISE 0x100
+int lg_diffuse_slice(int64_t N, int64_t D);
+int64_t lg_diffuse_workspace_bytes(int64_t B, int64_t N, int64_t D, int64_t hops, int flags, int backward);
+int lg_diffuse_fwd(const int32_t* nodetab, const int32_t* pairs, const float* x0, float* z_out, int64_t B, int64_t N,
+                   int64_t D, int64_t hops, float alpha, int flags, void* workspace, int64_t ws_bytes,
+                   lg_stream_t stream);
+int lg_diffuse_bwd(const int32_t* nodetab_t, const int32_t* pairs_t, const float* g, const float* x0, float* dx0_out,
+                   int64_t B, int64_t N, int64_t D, int64_t hops, float alpha, int flags, float scale_out,
+                   void* workspace, int64_t ws_bytes, lg_stream_t stream);
+
 /* Compressed layer-0 input (ABI 21).  The node init's non-sensor rows are dropout(relu(b)):
  * 632 of L-TOWN-A's 661 rows carry no information beyond their keep bits, yet materialising
  * x0 costs a 43 MB write and layer 0's forward and backward read it back (86 MB).

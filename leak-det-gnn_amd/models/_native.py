@@ -29,6 +29,7 @@ LG_F_F32_MFMA = 0x00400000  # lg_gcn_fwd_nm: the per-wave pipeline on exact f32 
 LG_F_BF16 = 0x40  # lg_gcn_fwd_nm / lg_gcn_bwd_nm / lg_edge_head_*: the bf16 node-MLP tier
 LG_F_PC = 0x00004000  # with LG_F_BF16: the producer / consumer forward (default: nm3)
 LG_F_BF16X3 = 0x00008000  # lg_gcn_fwd_nm fp32 tier: pc with the 3-way bf16 split (default: 2-way fp16 split)
+LG_F_DIFFUSE_HOPWISE = 0x100  # lg_diffuse_fwd / _bwd: one launch per hop (default: LDS-resident when the graph fits)
 LG_F_NM3 = 0x00020000  # lg_gcn_fwd_nm: the per-wave nm3 pipeline, 3-way bf16 split
 
 _i32, _i64, _u32, _u64, _f32, _p = (ctypes.c_int, ctypes.c_int64, ctypes.c_uint32, ctypes.c_uint64,
@@ -103,6 +104,11 @@ SIGNATURES = {
     "lg_add_layernorm_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _f32, _p]),
     "lg_layernorm_bwd_workspace_bytes": (_i64, [_i64]),
     "lg_layernorm_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _f32, _p, _i64, _p]),
+    # K-hop diffusion of the node init (csrc/diffuse.hip; added to ABI 26 without a bump)
+    "lg_diffuse_slice": (_i32, [_i64, _i64]),
+    "lg_diffuse_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i32, _i32]),
+    "lg_diffuse_fwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _i32, _p, _i64, _p]),
+    "lg_diffuse_bwd": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _i32, _f32, _p, _i64, _p]),
     "lg_gcn_bwd_nm_workspace_bytes": (_i64, [_i64]),
     "lg_gcn_bwd_nm": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _f32, _f32, _p, _i64, _p]),
     "lg_edge_head_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i32, _f32,

@@ -180,7 +180,7 @@ class LeakDetector(nn.Module):
                  use_time: bool = True, include_links: Sequence[str] = ("PIPES", "PUMPS", "VALVES"),
                  mlp_dtype: str = "fp32", sensor_layers: int = 1, sensor_dropout: float = 0.0,
                  edge_weight: Optional[torch.Tensor] = None, learn_edge_weight: bool = False,
-                 skip: str = "none", norm: str = "none") -> None:
+                 skip: str = "none", norm: str = "none", diffuse_hops: int = 0, diffuse_alpha: float = 0.1) -> None:
         """edge_weight: None, or a positive floating (n_links,) tensor, one weight per link in the
         order of the link table build_wdn_graph_from_inp walks (utils.link_edge_weights builds one
         from the .inp file); link j is the directed edges 2j and 2j + 1 of edge_index_single.
@@ -189,8 +189,22 @@ class LeakDetector(nn.Module):
         skip: "none", or "residual": every GCN layer x = x + dropout(relu(conv(x))).  An attribute
         like mlp_dtype: no parameter, no state-dict entry.
         norm: "none", or "layer" (needs skip="residual"): pre-norm, a LayerNorm in front of every
-        branch and of the heads; adds `norms` (gnn_layers + 1 nn.LayerNorm(node_hidden))."""
+        branch and of the heads; adds `norms` (gnn_layers + 1 nn.LayerNorm(node_hidden)).
+        diffuse_hops, diffuse_alpha: K > 0 propagates the node init K hops before layer 0, z_{k+1} =
+        (1 - alpha) Ahat z_k + alpha x_0 (APPNP; leakgnn::diffuse): reach gnn_layers + K with no
+        parameter.  Attributes like skip: no state-dict entry; 0: the detector without them."""
         super().__init__()
+        if not isinstance(diffuse_hops, int) or not 0 <= diffuse_hops <= 64:
+            raise ValueError(f"diffuse_hops must be an integer in 0..64, got {diffuse_hops!r}")
+        if not 0.0 <= float(diffuse_alpha) <= 1.0:
+            raise ValueError(f"diffuse_alpha must be in [0, 1], got {diffuse_alpha!r}")
+        if diffuse_hops > 0 and mlp_dtype == "bf16":
+            raise NotImplementedError("diffuse_hops > 0 needs mlp_dtype='fp32': the hops run on the fp32-tier "
+                                      "node-major trunk (lg_diffuse_fwd / lg_diffuse_bwd) only")
+        if diffuse_hops > 0 and learn_edge_weight:
+            raise NotImplementedError("diffuse_hops > 0 takes fixed edge weights only: the weight gradient through "
+                                      "the hops would need every z_k saved and is not built")
+        self.diffuse_hops, self.diffuse_alpha = int(diffuse_hops), float(diffuse_alpha)
         if skip not in ("none", "residual"):
             raise ValueError(f"skip must be 'none' or 'residual', got {skip!r}")
         if skip == "residual" and mlp_dtype == "bf16":
@@ -367,6 +381,8 @@ class LeakDetector(nn.Module):
             return False
         if self.skip != "none":  # the skip is not folded into encoder_trunk and the X0 kernels
             return False
+        if self.diffuse_hops:  # nor is the diffusion stage: it needs the dense node init
+            return False
         if self.capture is not None:  # the capture reads h_s, which the fused op never forms
             return False
         if residual.requires_grad or (tfeat is not None and self.sensor_encoder.use_time and tfeat.requires_grad):
@@ -397,6 +413,14 @@ class LeakDetector(nn.Module):
         h0 = torch.cat([h_s.index_select(1, slot.clamp(min=0).long()) * has, has.expand(B, N, 1)], dim=-1)
         p = float(self.dropout.p)
         x = F.dropout(F.relu(self.sensor_to_node(h0)), p, self.training).reshape(B * N, -1)
+        if self.diffuse_hops:  # the hops composed from the width-general propagate, window by window
+            g, a = graph, self.diffuse_alpha
+            x0 = x.view(B, N, -1).transpose(0, 1).reshape(N, -1)  # [N][B * D]: one propagate serves every window
+            z = x0
+            for _ in range(self.diffuse_hops):
+                z = (1.0 - a) * torch.ops.leakgnn.spmm_cols(z, None, g.rowptr, g.col, g.w, g.rowptr_t, g.col_t,
+                                                            g.w_t) + a * x0
+            x = z.view(N, B, -1).transpose(0, 1).reshape(B * N, -1)
         ei = self._batched_edges.get((B, dev))
         if ei is None:
             ei = _batchify_edge_index(self.edge_index_single.to(dev), N, B)
@@ -435,8 +459,10 @@ class LeakDetector(nn.Module):
         Wn, bn = f(self.sensor_to_node.weight), f(self.sensor_to_node.bias)  # (D, Ds+1), (D,)
         N, D = len(self.node_names), Wn.shape[0]
         skip = self.skip == "residual"
-        # a skip model takes the node-major layout at every B, as the bf16 tier does
-        nm = ops.use_node_major(B, N, D, bf16=self.mlp_dtype == "bf16" or skip)
+        hops = self.diffuse_hops
+        dkw = {"hops": hops, "alpha": self.diffuse_alpha} if hops else {}  # absent at 0: the op as before
+        # a skip or diffusion model takes the node-major layout at every B, as the bf16 tier does
+        nm = ops.use_node_major(B, N, D, bf16=self.mlp_dtype == "bf16" or skip or hops > 0)
         drop = self.training and float(self.dropout.p) > 0.0
         g = graph
         bf16 = self.mlp_dtype == "bf16"
@@ -467,14 +493,15 @@ class LeakDetector(nn.Module):
                     h_s.retain_grad()
                 self.capture["h_s"] = h_s
             # sensor_to_node (rows with a sensor: [h_s, 1] W^T + b; without: b) folded into node init
-            mk = self._x0marks(g, slot) if (nm and self.compress_x0 and len(self.convs) > 1 and not skip) else None
+            mk = (self._x0marks(g, slot)
+                  if (nm and self.compress_x0 and len(self.convs) > 1 and not skip and not hops) else None)
             if self.norm == "layer":
                 trunk = library.trunk_fields("gnn_trunk_norm", torch.ops.leakgnn.gnn_trunk_norm(
                     h_s, Wn, bn, [f(c.lin.weight) for c in self.convs], [f(c.bias) for c in self.convs],
                     [f(n.weight) for n in self.norms], [f(n.bias) for n in self.norms], slot, sensor_idx, nonsensor,
                     slot_live, g.nodetab, g.pairs, g.rowptr, g.col, g.nodetab_t, g.pairs_t,
                     float(self.dropout.p) if drop else 0.0, float(self.norms[0].eps),
-                    library.seed_tensor(residual.device) if drop else _NO_SEED, edge_w))
+                    library.seed_tensor(residual.device) if drop else _NO_SEED, edge_w, **dkw), hops > 0)
             else:
                 trunk = library.trunk_fields("gnn_trunk", torch.ops.leakgnn.gnn_trunk(
                     h_s, Wn, bn, [f(c.lin.weight) for c in self.convs], [f(c.bias) for c in self.convs], slot, sensor_idx,
@@ -482,7 +509,8 @@ class LeakDetector(nn.Module):
                     g.col_t, g.w_t, float(self.dropout.p) if drop else 0.0, nm,
                     library.seed_tensor(residual.device) if drop else _NO_SEED,
                     mk.nodetab_s if mk is not None else None, mk.pairs_s if mk is not None else None,
-                    mk.pos_slot_t if mk is not None else None, edge_w, bf16=bf16, **({"skip": True} if skip else {})))
+                    mk.pos_slot_t if mk is not None else None, edge_w, bf16=bf16, **({"skip": True} if skip else {}),
+                    **dkw), hops > 0)
         # xs: x_0 (its sensor rows while x0bits is non-empty) .. x_L; xns: under norm="layer" xn_0 .. xn_L
         xs, xns, ymask, x0bits = trunk.xs, trunk.xns, trunk.ymask, trunk.x0bits
         # (N, B, D) node-major, else (B, N, D); under norm="layer" the last norm's output
@@ -510,6 +538,8 @@ class LeakDetector(nn.Module):
                 self.capture["fmask"] = [_unpack_mask(w, N, B, D) for w in ymask.view(nl, -1)] if nl else []
             if self.norm == "layer":  # the branches' inputs and the heads' (xs stays the residual stream)
                 self.capture["xns"] = xns
+            if hops:  # the diffused node init z_K: layer 0's input, or the residual stream's start
+                self.capture["z"] = trunk.z
         return out[0]
 
 
@@ -538,18 +568,21 @@ def detector_from_args(inp_path: str | Path, sensor_ids: Sequence[str], pipe_ids
     (utils.link_edge_weights) and "learn_edge_weight"; a missing key is the unweighted detector.
     "gnn_layers" (default 2) and "skip" in {none, residual} (default none): a missing key is the
     two-layer plain trunk, so checkpoints from before these flags load as before.  "norm" in {none,
-    layer} (default none) likewise.
+    layer} (default none) likewise, and so are "diffuse_hops" (default 0) and "diffuse_alpha" (0.1).
     cls: the class to build (the caller's own LeakDetector name; default: this module's)."""
     args = args or {}
     mode = args.get("edge_weight") or "none"
     ew = link_edge_weights(inp_path, mode=mode) if mode != "none" else None
     skip = args.get("skip") or "none"
     norm = args.get("norm") or "none"
+    hops = int(args.get("diffuse_hops") or 0)
+    alpha = args.get("diffuse_alpha")
+    dkw = {"diffuse_hops": hops, "diffuse_alpha": 0.1 if alpha is None else float(alpha)} if hops else {}
     return (cls or LeakDetector)(inp_path, sensor_ids, pipe_ids_in_order, sensor_hidden=64, node_hidden=64,
                                  gnn_layers=int(args.get("gnn_layers") or 2), dropout=0.1, use_time=True,
                                  edge_weight=ew, learn_edge_weight=bool(args.get("learn_edge_weight", False)),
                                  **({"skip": skip} if skip != "none" else {}),
-                                 **({"norm": norm} if norm != "none" else {}), **kwargs)
+                                 **({"norm": norm} if norm != "none" else {}), **dkw, **kwargs)
 
 
 def detector_from_checkpoint(ckpt: dict, inp_path: str | Path, **kwargs) -> LeakDetector:

@@ -16,7 +16,9 @@ ordinary ops (fake / meta implementations give output shapes without running ker
   leakgnn::gru_stack           the same with num_layers > 1 (dense-input upper layers, inter-layer dropout)
   leakgnn::gru_predictor       NormalPredictorGRU's nn.GRU over a dense (B, L, I) input (MFMA layers at H = 128)
   leakgnn::tcn_predictor       NormalPredictorTCN's conv stack over the projected (B, L, 128) input, for training
-  leakgnn::gnn_trunk           node init + L x [GCNConv, ReLU, Dropout] (detector.py:178-201); skip=True: identity skips
+  leakgnn::diffuse             K-hop personalised-PageRank propagation of a node-major tensor (lg_diffuse_fwd)
+  leakgnn::gnn_trunk           node init + L x [GCNConv, ReLU, Dropout] (detector.py:178-201); skip=True: identity skips;
+                               hops > 0: leakgnn::diffuse's stage between the node init and layer 0
   leakgnn::gnn_trunk_norm      the same with a LayerNorm before every residual branch and before the heads
   leakgnn::encoder_trunk       gru_encoder + gnn_trunk as one op (node-major, compressed node init)
   leakgnn::detector_heads      pipe gather + EdgeHead + mean pool + NoLeakHead
@@ -1083,6 +1085,88 @@ def expand_x0(xs0: Tensor, x0bits: Tensor, sensor_slot: Tensor, node_bias: Tenso
     return x0
 
 
+# ============================================================================ diffuse
+# APPNP's propagation (Gasteiger et al. 2019) of a node-major tensor: z_0 = x, z_{k+1} = (1 - alpha)
+# Ahat z_k + alpha x.  No parameter; the backward is the adjoint recurrence over the transposed
+# tables and saves nothing but them.
+def check_diffuse(hops: int, alpha: float, zero_ok: bool = False) -> None:
+    if not (0 if zero_ok else 1) <= int(hops) <= 64:
+        raise ValueError(f"diffuse hops must be in {0 if zero_ok else 1}..64, got {hops}")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"diffuse alpha must be in [0, 1], got {alpha}")
+
+
+def _diffuse_launch(lib, tab: Tensor, pairs: Tensor, src: Tensor, out: Tensor, hops: int, alpha: float, *,
+                    backward: bool, x0: Optional[Tensor] = None, scale_out: float = 1.0, flags: int = 0) -> None:
+    """lg_diffuse_fwd (src = x_0) or lg_diffuse_bwd (src = g; x0: apply the node init's mask
+    [x0 > 0] * scale_out) on (N, B, D) tensors, with the hop-wise form's workspace when it runs."""
+    N, B, D = src.shape
+    st = stream_of(src)
+    flags |= nat.LG_F_MASK_OUT if x0 is not None else 0
+    nb = int(lib.lg_diffuse_workspace_bytes(B, N, D, hops, flags, int(backward)))
+    if nb < 0:
+        check(nb, "lg_diffuse_workspace_bytes")
+    ws = torch.empty(nb, device=src.device, dtype=torch.uint8) if nb else None
+    with _timed("diffuse_bwd" if backward else "diffuse_fwd", src.device):
+        if backward:
+            check(lib.lg_diffuse_bwd(ptr(tab), ptr(pairs), ptr(src), ptr(x0), ptr(out), B, N, D, hops, alpha, flags,
+                                     scale_out, ptr(ws), nb, st), "lg_diffuse_bwd")
+        else:
+            check(lib.lg_diffuse_fwd(ptr(tab), ptr(pairs), ptr(src), ptr(out), B, N, D, hops, alpha, flags, ptr(ws),
+                                     nb, st), "lg_diffuse_fwd")
+
+
+@torch.library.custom_op(f"{NS}::diffuse", mutates_args=(), device_types="cuda")
+def diffuse(x: Tensor, nodetab: Tensor, pairs: Tensor, nodetab_t: Tensor, pairs_t: Tensor, hops: int,
+            alpha: float) -> Tensor:
+    """z_hops of z_0 = x, z_{k+1} = (1 - alpha) Ahat z_k + alpha x, for node-major x (N, B, D), D in
+    {32, 64}; Ahat from GCNGraph's node tables (edge weights included).  hops in 1..64, alpha in [0, 1]."""
+    lib = load_library()
+    x = _c(x)
+    _req(x)
+    if x.dim() != 3:
+        raise ValueError(f"diffuse: x must be node-major (N, B, D), got {tuple(x.shape)}")
+    _check_d(x.shape[2])
+    check_diffuse(hops, alpha)
+    z = torch.empty_like(x)
+    _diffuse_launch(lib, nodetab, pairs, x, z, hops, alpha, backward=False)
+    return z
+
+
+@diffuse.register_fake
+def _(x, nodetab, pairs, nodetab_t, pairs_t, hops, alpha):
+    return torch.empty_like(x)
+
+
+@torch.library.custom_op(f"{NS}::diffuse_backward", mutates_args=(), device_types="cuda")
+def diffuse_backward(g: Tensor, nodetab_t: Tensor, pairs_t: Tensor, hops: int, alpha: float) -> Tensor:
+    """dx of diffuse: u = g, acc = 0; hops times acc += alpha u, u = (1 - alpha) Ahat^T u; u + acc."""
+    lib = load_library()
+    g = _c(g)
+    _req(g)
+    dx = torch.empty_like(g)
+    _diffuse_launch(lib, nodetab_t, pairs_t, g, dx, hops, alpha, backward=True)
+    return dx
+
+
+@diffuse_backward.register_fake
+def _(g, nodetab_t, pairs_t, hops, alpha):
+    return torch.empty_like(g)
+
+
+def _diffuse_setup(ctx, inputs, output):
+    _, _, _, nodetab_t, pairs_t, ctx.hops, ctx.alpha = inputs
+    ctx.save_for_backward(nodetab_t, pairs_t)
+
+
+def _diffuse_bwd(ctx, g):
+    nodetab_t, pairs_t = ctx.saved_tensors
+    return (torch.ops.leakgnn.diffuse_backward(g, nodetab_t, pairs_t, ctx.hops, ctx.alpha),) + (None,) * 6
+
+
+diffuse.register_autograd(_diffuse_bwd, setup_context=_diffuse_setup)
+
+
 # ============================================================================ trunk ops: shared drivers
 # gnn_trunk, gnn_trunk_norm and encoder_trunk are one forward layer launch (_layer_forward) and one
 # backward layer launch (_layer_backward) over the C entry points, each op call described once by a
@@ -1108,7 +1192,8 @@ def _layer_words(ymask: Tensor, l: int, L: int) -> Tensor:  # of a ymask with on
 # CSR triple where window-major needs it, their transposes in a backward, the sensor marks.
 _Trunk = dataclasses.make_dataclass("_Trunk", (
     ["lib", "st", "dev", "B", "N", "S", "D", "L", "p", "scale", "drop"]
-    + [("node_major", bool, True), ("bf16", bool, False), ("skip", bool, False), ("nnz", int, 0)]
+    + [("node_major", bool, True), ("bf16", bool, False), ("skip", bool, False), ("nnz", int, 0),
+       ("hops", int, 0), ("alpha", float, 0.0)]
     + [(k, Optional[Tensor], None) for k in (
         "nodetab", "pairs", "rowptr", "col", "w", "nodetab_t", "pairs_t", "rowptr_t", "col_t", "w_t",
         "nodetab_s", "pairs_s", "pos_slot_t", "sensor_slot", "node_bias")]))
@@ -1120,6 +1205,26 @@ def _trunk(lib, ref: Tensor, B: int, N: int, S: int, D: int, L: int, p: float, s
     seed_v, sbit = _seed_args(seed) if (drop and seed is not None) else (0, 0)
     return _Trunk(lib=lib, st=stream_of(ref), dev=ref.device, B=B, N=N, S=S, D=D, L=L, p=p,
                   scale=1.0 / (1.0 - p) if drop else 1.0, drop=(nat.LG_F_DROPOUT if drop else 0, seed_v, sbit), **kw)
+
+
+def _check_trunk_diffuse(op: str, hops: int, alpha: float, node_major: bool = True, bf16: bool = False) -> None:
+    check_diffuse(hops, alpha, zero_ok=True)
+    if hops > 0 and (bf16 or not node_major):
+        raise ValueError(f"{op}: hops > 0 runs on the node-major fp32 tier only")
+
+
+def _trunk_diffuse_forward(t: _Trunk, x0: Tensor, z: Tensor) -> None:
+    """The diffusion stage of a trunk op (t.hops > 0), between the node init and layer 0: z = z_K of
+    the dense node-major node init x0."""
+    _diffuse_launch(t.lib, t.nodetab, t.pairs, x0, z, t.hops, t.alpha, backward=False)
+
+
+def _trunk_diffuse_backward(t: _Trunk, dz: Tensor, x0: Tensor, nonsensor_idx: Tensor) -> Tuple[Tensor, Tensor]:
+    """(dx0, dbias_ns) from dL/dz: the adjoint hops, then the node init's ReLU / dropout mask from the
+    saved x0 inside the same launch (LG_F_MASK_OUT); dbias_ns: the non-sensor rows' bias sum."""
+    dx0 = torch.empty_like(dz)
+    _diffuse_launch(t.lib, t.nodetab_t, t.pairs_t, dz, dx0, t.hops, t.alpha, backward=True, x0=x0, scale_out=t.scale)
+    return dx0, dx0.index_select(0, nonsensor_idx).sum(dim=(0, 1))
 
 
 def _layer_forward(t: _Trunk, l: int, x: Tensor, W: Tensor, b: Tensor, y: Tensor, words: Optional[Tensor] = None, *,
@@ -1227,14 +1332,17 @@ def _layer_backward(t: _Trunk, l: int, dy: Tensor, x: Tensor, y: Optional[Tensor
     return dx, dW, db
 
 
-def _trunk_layer_launches(t: _Trunk, dy: Tensor, xs, ymask: Tensor, weights, x0bits: Optional[Tensor], wgrad: _WGrad):
+def _trunk_layer_launches(t: _Trunk, dy: Tensor, xs, ymask: Tensor, weights, x0bits: Optional[Tensor], wgrad: _WGrad,
+                          z: Optional[Tensor] = None):
     """The GCN layers' backward of gnn_trunk and encoder_trunk, last first: (dx0, [dW_l], [db_l],
     dbias_ns, workspaces).  dx0: the node init's pre-activation gradient (layer 0's dx: masked by
     the node init's ReLU / dropout; under x0bits the sensor nodes' rows only); dbias_ns: its
     non-sensor rows' sum.  Plain: the last layer masks its output ([x_L > 0], from ymask's bits
     where the forward wrote them), every layer its input.  t.skip: x_{l+1} = x_l + f_l, so
     dx_l = dx_{l+1} + (branch); every layer applies its own mask (LG_F_MASK_IN on its bit words)
-    and only layer 0 a LG_F_MASK_OUT, the node init's."""
+    and only layer 0 a LG_F_MASK_OUT, the node init's.  z (t.hops > 0): layer 0's input is the
+    diffused z_K, no ReLU output: its launch runs without LG_F_MASK_OUT, node_slot and dnode_bias and
+    returns dL/dz in full (_trunk_diffuse_backward applies the node init's mask)."""
     L, D, lib = t.L, t.D, t.lib
     wsb = lib.lg_gcn_bwd_nm_workspace_bytes(D) if t.node_major else lib.lg_gcn_bwd_workspace_bytes(D)
     # one workspace per layer: the layers' slab reductions run together at the batch flush
@@ -1245,9 +1353,11 @@ def _trunk_layer_launches(t: _Trunk, dy: Tensor, xs, ymask: Tensor, weights, x0b
         last = l == L - 1
         words = (_layer_words(ymask, l, L) if t.skip else  # else [x_L > 0] as bits
                  ymask if (t.node_major and last and ymask.numel() > 0) else None)
+        at_z = l == 0 and z is not None
         dy, dWs[l], dbs[l] = _layer_backward(
-            t, l, dy, xs[l], None if t.skip else xs[l + 1], weights[l], words, wss[l], mask_in=last or t.skip,
-            mask_out=l == 0 or not t.skip, scale_out=t.scale, dbias_ns=dbias_ns if l == 0 else None,
+            t, l, dy, z if at_z else xs[l], None if t.skip else xs[l + 1], weights[l], words, wss[l],
+            mask_in=last or t.skip, mask_out=(l == 0 or not t.skip) and not at_z, scale_out=t.scale,
+            dbias_ns=dbias_ns if (l == 0 and not at_z) else None,
             x0bits=x0bits if l == 0 else None, wgrad=wgrad)  # dx: already masked by the previous op's relu/dropout
     return dy, dWs, dbs, dbias_ns, wss
 
@@ -1279,20 +1389,24 @@ def _alloc(lay, like: Tensor) -> List[Tensor]:
     return [like.new_empty(shape, dtype=dt) for shape, dt in lay[0]]  # (a fake tensor gives fake ones)
 
 
-def _gnn_trunk_layout(L, B=0, N=0, S=0, D=0, node_major=True, skip=False, x0c=False):
-    """[x_0, ..., x_L, ymask, x0bits]; x_L is the heads' input.  x0c: x_0 is its sensor rows."""
+def _gnn_trunk_layout(L, B=0, N=0, S=0, D=0, node_major=True, skip=False, x0c=False, diffuse=False):
+    """[x_0, ..., x_L, ymask, x0bits]; x_L is the heads' input.  x0c: x_0 is its sensor rows.
+    diffuse (hops > 0): one more entry, z = z_K, layer 0's input (the heads' at L == 0)."""
     act = (N, B, D) if node_major else (B, N, D)
     nmask = mask_words(N, B) if (node_major and L > 0) else 0
     return ([((S, B, D) if x0c else act, _F32)] + [(act, _F32)] * L
-            + [((nmask * (L if skip else 1),), _I16), ((nmask if x0c else 0,), _I16)],
-            dict(xs=list(range(L + 1)), xns=None, ymask=L + 1, x0bits=L + 2, h=L))
+            + [((nmask * (L if skip else 1),), _I16), ((nmask if x0c else 0,), _I16)] + [(act, _F32)] * bool(diffuse),
+            dict(xs=list(range(L + 1)), xns=None, ymask=L + 1, x0bits=L + 2, h=L if (L or not diffuse) else L + 3,
+                 **(dict(z=L + 3) if diffuse else {})))
 
 
-def _gnn_trunk_norm_layout(L, B=0, N=0, D=0):
-    """[xn_L, x_0 .. x_L, xn_0 .. xn_{L-1}, stats, ymask]; xn_L is the heads' input."""
-    return ([((N, B, D), _F32)] * (2 * L + 2) + [((L + 1, N * B, 2), _F32), ((mask_words(N, B) * L,), _I16)],
+def _gnn_trunk_norm_layout(L, B=0, N=0, D=0, diffuse=False):
+    """[xn_L, x_0 .. x_L, xn_0 .. xn_{L-1}, stats, ymask]; xn_L is the heads' input.  diffuse (hops >
+    0): one more entry, z = z_K, the residual stream's start (x_1 = z + f_0; x_0 stays the node init)."""
+    return ([((N, B, D), _F32)] * (2 * L + 2) + [((L + 1, N * B, 2), _F32), ((mask_words(N, B) * L,), _I16)]
+            + [((N, B, D), _F32)] * bool(diffuse),
             dict(xs=list(range(1, L + 2)), xns=list(range(L + 2, 2 * L + 2)) + [0], ymask=2 * L + 3, x0bits=None, h=0,
-                 stats=2 * L + 2))
+                 stats=2 * L + 2, **(dict(z=2 * L + 4) if diffuse else {})))
 
 
 def _encoder_trunk_layout(L, B=0, N=0, S=0, D=0, Lw=0, H=0, save=False):
@@ -1304,25 +1418,28 @@ def _encoder_trunk_layout(L, B=0, N=0, S=0, D=0, Lw=0, H=0, save=False):
             dict(xs=[L + 1] + list(range(L)), xns=None, ymask=L, x0bits=L + 2, h=L - 1, h_seq=L + 3, gates=L + 4))
 
 
-_LAYOUTS = {"gnn_trunk": (_gnn_trunk_layout, lambda n: n - 3),  # op -> (layout, L of an output count)
-            "gnn_trunk_norm": (_gnn_trunk_norm_layout, lambda n: (n - 4) // 2),
+# op -> (layout, L of an output count; diffuse: the count includes z)
+_LAYOUTS = {"gnn_trunk": (_gnn_trunk_layout, lambda n, diffuse=False: n - 3 - diffuse),
+            "gnn_trunk_norm": (_gnn_trunk_norm_layout, lambda n, diffuse=False: (n - 4 - diffuse) // 2),
             "encoder_trunk": (_encoder_trunk_layout, lambda n: n - 5)}
 
 
 # A trunk op's outputs by name: xs = x_0 .. x_L (x_0 its sensor rows where x0bits is non-empty), xns =
 # xn_0 .. xn_L (gnn_trunk_norm), the mask words, h = the heads' input; then the ops' own.  None: no such output.
-TrunkOut = namedtuple("TrunkOut", "xs xns ymask x0bits h stats h_seq gates", defaults=(None, None, None))
+# z: the diffused node init z_K (gnn_trunk / gnn_trunk_norm with hops > 0).
+TrunkOut = namedtuple("TrunkOut", "xs xns ymask x0bits h stats h_seq gates z", defaults=(None, None, None, None))
 
 
-def _positions(op: str, n_out: int) -> Dict[str, object]:  # (no cache: torch.compile traces through here)
+def _positions(op: str, n_out: int, diffuse: bool = False) -> Dict[str, object]:  # (no cache: torch.compile traces through here)
     layout, layers = _LAYOUTS[op]
-    return layout(layers(n_out))[1]
+    return layout(layers(n_out, True), diffuse=True)[1] if diffuse else layout(layers(n_out))[1]
 
 
-def trunk_fields(op: str, out) -> TrunkOut:
-    """The flat output list of leakgnn::<op> (gnn_trunk, gnn_trunk_norm, encoder_trunk) by name."""
+def trunk_fields(op: str, out, diffuse: bool = False) -> TrunkOut:
+    """The flat output list of leakgnn::<op> (gnn_trunk, gnn_trunk_norm, encoder_trunk) by name.
+    diffuse: the op ran with hops > 0 (the list ends in z)."""
     return TrunkOut(**{k: None if i is None else out[i] if isinstance(i, int) else [out[j] for j in i]
-                       for k, i in _positions(op, len(out)).items()})
+                       for k, i in _positions(op, len(out), diffuse).items()})
 
 
 # ---------------------------------------------------------------------------- autograd glue
@@ -1370,17 +1487,20 @@ def _named_grads(op, n_seen: int, **grads) -> tuple:
     return tuple(grads.get(name) for name in names[:n_seen])
 
 
-def _trunk_ctx(ctx, op, inputs, output) -> Tuple[Dict[str, object], TrunkOut]:
+def _trunk_ctx(ctx, op, inputs, output, hops: int = 0) -> Tuple[Dict[str, object], TrunkOut]:
     """The trunk ops' setup_context in common; returns (inputs by name, outputs by name).  Sets ctx.w_grad, ctx.n_in
     and ctx.h: the position of the heads' input, the one differentiable output (the rest serve the backward)."""
     a, name = dict(zip(_positional(op)[0], inputs)), op._qualname.split("::")[1]
     # learned edge weights (requires_grad, not needs_input_grad: that tuple is flat over the tensor lists here)
     ctx.w_grad = a["edge_w"] is not None and a["edge_w"].requires_grad
     ctx.n_in = _args_seen(op, inputs)
-    ctx.h = _positions(name, len(output))["h"]
+    if ctx.w_grad and hops > 0:
+        raise NotImplementedError(f"{name}: the gradient of edge_w through the diffusion hops is not built "
+                                  "(it would need every z_k saved): hops > 0 takes fixed edge weights only")
+    ctx.h = _positions(name, len(output), hops > 0)["h"]
     ctx.mark_non_differentiable(*(o for i, o in enumerate(output) if i != ctx.h))
     ctx.set_materialize_grads(False)  # their gradients would be zero-filled (B, N, D) tensors
-    return a, trunk_fields(name, output)
+    return a, trunk_fields(name, output, hops > 0)
 
 
 # ============================================================================ gnn_trunk
@@ -1401,7 +1521,8 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
               nodetab: Tensor, pairs: Tensor, rowptr: Tensor, col: Tensor, w: Tensor, nodetab_t: Tensor,
               pairs_t: Tensor, rowptr_t: Tensor, col_t: Tensor, w_t: Tensor, p: float, node_major: bool, seed: Tensor,
               nodetab_s: Optional[Tensor], pairs_s: Optional[Tensor], pos_slot_t: Optional[Tensor],
-              edge_w: Optional[Tensor] = None, *, bf16: bool = False, skip: bool = False) -> List[Tensor]:
+              edge_w: Optional[Tensor] = None, *, bf16: bool = False, skip: bool = False, hops: int = 0,
+              alpha: float = 0.0) -> List[Tensor]:
     """[x_0, ..., x_L, ymask, x0bits]: sensor_to_node + node init (detector.py:160, 178-190),
     then L x dropout(relu(GCNConv)).
 
@@ -1427,7 +1548,11 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
       x_{l+1} = x_l + dropout(relu(Ahat x_l W_l^T + b_l))                  (lg_gcn_fwd_nm_skip)
     on the node-major fp32 tier with the dense node init.  [x_{l+1} > 0] is then no longer the
     branch's ReLU/dropout mask, so EVERY layer keeps its [f > 0] bits: ymask is (L * nmask,),
-    layer l's words at [l * nmask, (l + 1) * nmask) (each 1/32 of an activation)."""
+    layer l's words at [l * nmask, (l + 1) * nmask) (each 1/32 of an activation).
+    hops, alpha (keyword-only, as skip): hops > 0 puts leakgnn::diffuse's stage between the node init
+    and layer 0, z = z_hops of x_0 (lg_diffuse_fwd), on the node-major fp32 tier with the dense node
+    init; the list gains z as its last entry, layer 0's input (the heads' at L == 0).  hops == 0:
+    the layout, the saved state and the launches are the op's without the keywords."""
     lib = load_library()
     h_s, proj_weight, node_bias = _c(h_s), _c(proj_weight), _c(node_bias)
     weights, biases = [_c(t) for t in weights], [_c(t) for t in biases]
@@ -1439,16 +1564,17 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
         raise ValueError("gnn_trunk: the bf16 tier runs on the node-major layout only")
     if skip and (bf16 or not node_major):
         raise ValueError("gnn_trunk: skip=True runs on the node-major fp32 tier only")
+    _check_trunk_diffuse("gnn_trunk", hops, alpha, node_major, bf16)
     if tuple(proj_weight.shape) != (D, Ds + 1):
         raise ValueError(f"proj_weight must be (D, Ds + 1) = ({D}, {Ds + 1}), got {tuple(proj_weight.shape)}")
     N, L = sensor_slot.shape[0], len(weights)
-    x0c = _compress_x0(nodetab_s, node_major, L) and not skip
+    x0c = _compress_x0(nodetab_s, node_major, L) and not skip and not hops
     t = _trunk(lib, h_s, B, N, S, D, L, p, seed, node_major=node_major, bf16=bf16, skip=skip, nnz=col.numel(),
                nodetab=nodetab, pairs=pairs, rowptr=rowptr, col=col, w=w, nodetab_s=nodetab_s, pairs_s=pairs_s,
-               node_bias=node_bias)
+               node_bias=node_bias, hops=hops, alpha=alpha)
     dflag, seed_v, sbit = t.drop
-    out = _alloc(_gnn_trunk_layout(L, B, N, S, D, node_major, skip, x0c), h_s)
-    f = trunk_fields("gnn_trunk", out)
+    out = _alloc(_gnn_trunk_layout(L, B, N, S, D, node_major, skip, x0c, hops > 0), h_s)
+    f = trunk_fields("gnn_trunk", out, hops > 0)
     with _timed("node_init", t.dev):
         if x0c:
             check(lib.lg_node_init_bits_fwd(ptr(sensor_slot), ptr(sensor_idx), ptr(h_s), ptr(proj_weight),
@@ -1459,21 +1585,23 @@ def gnn_trunk(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights: List
                                             ptr(node_bias), ptr(f.xs[0]), B, N, S, Ds, D,
                                             dflag | (nat.LG_F_NODE_MAJOR if node_major else 0), p, seed_v, 0 | sbit,
                                             t.st), "lg_node_init_proj_fwd")
+    if hops:
+        _trunk_diffuse_forward(t, f.xs[0], f.z)
     for l, (W, b) in enumerate(zip(weights, biases)):
         words = _layer_words(f.ymask, l, L) if skip else f.ymask if (node_major and l == L - 1) else None
-        _layer_forward(t, l, f.xs[l], W, b, f.xs[l + 1], words, x0bits=f.x0bits if (x0c and l == 0) else None,
-                       branch=skip)
+        _layer_forward(t, l, f.z if (hops and l == 0) else f.xs[l], W, b, f.xs[l + 1], words,
+                       x0bits=f.x0bits if (x0c and l == 0) else None, branch=skip)
     return out
 
 
 @gnn_trunk.register_fake
 def _(h_s, proj_weight, node_bias, weights, biases, sensor_slot, sensor_idx, nonsensor_idx, slot_live, nodetab, pairs,
       rowptr, col, w, nodetab_t, pairs_t, rowptr_t, col_t, w_t, p, node_major, seed, nodetab_s, pairs_s, pos_slot_t,
-      edge_w=None, *, bf16=False, skip=False):
+      edge_w=None, *, bf16=False, skip=False, hops=0, alpha=0.0):
     L = len(weights)
-    x0c = _compress_x0(nodetab_s, node_major, L) and not skip
+    x0c = _compress_x0(nodetab_s, node_major, L) and not skip and not hops
     return _alloc(_gnn_trunk_layout(L, h_s.shape[0], sensor_slot.shape[0], h_s.shape[1], proj_weight.shape[0],
-                                    node_major, skip, x0c), h_s)
+                                    node_major, skip, x0c, hops > 0), h_s)
 
 
 @torch.library.custom_op(f"{NS}::gnn_trunk_backward", mutates_args=(), device_types="cuda")
@@ -1483,8 +1611,8 @@ def gnn_trunk_backward(grad_out: Tensor, xs: List[Tensor], ymask: Tensor, h_s: T
                        nodetab_t: Tensor, pairs_t: Tensor, rowptr_t: Tensor, col_t: Tensor, w_t: Tensor, p: float,
                        node_major: bool, x0bits: Optional[Tensor], x0_bias: Optional[Tensor],
                        pos_slot_t: Optional[Tensor], rowptr: Optional[Tensor] = None, col: Optional[Tensor] = None,
-                       *, bf16: bool = False, skip: bool = False
-                       ) -> Tuple[Tensor, Tensor, Tensor, List[Tensor], List[Tensor], Tensor]:
+                       z: Optional[Tensor] = None, *, bf16: bool = False, skip: bool = False, hops: int = 0,
+                       alpha: float = 0.0) -> Tuple[Tensor, Tensor, Tensor, List[Tensor], List[Tensor], Tensor]:
     """(dh_s, dproj_weight, dnode_bias, [dW_l], [db_l], dw): one fused lg_gcn_bwd[_nm] per layer,
     last first (ReLU/dropout masks of a layer's output and input applied inside the kernel
     from the saved activations; the non-sensor rows' node-bias gradient summed inside layer
@@ -1494,17 +1622,22 @@ def gnn_trunk_backward(grad_out: Tensor, xs: List[Tensor], ymask: Tensor, h_s: T
     it through lg_gcn_bwd_nm_x0.  rowptr, col (the FORWARD CSR): the edge coefficients learn, and
     dw is dL/dw over its slots (sum over the layers of _layer_dw); otherwise dw is empty.
     skip: gnn_trunk's identity skips (lg_gcn_bwd_nm_skip per layer, every layer's mask from its own
-    words of ymask)."""
+    words of ymask).  z, hops, alpha: gnn_trunk's diffusion stage (z = z_hops, layer 0's input): layer 0
+    returns dL/dz unmasked, then ONE lg_diffuse_bwd runs the adjoint hops and applies the node init's
+    mask from xs[0]; the non-sensor rows' bias sum is the torch expression of L == 0."""
     lib = load_library()
     L = len(weights)
     N, B, D = xs[-1].shape if node_major else xs[0].transpose(0, 1).shape
     t = _trunk(lib, grad_out, B, N, h_s.shape[1], D, L, p, node_major=node_major, bf16=bf16, skip=skip,
                nodetab_t=nodetab_t, pairs_t=pairs_t, rowptr_t=rowptr_t, col_t=col_t, w_t=w_t, pos_slot_t=pos_slot_t,
-               sensor_slot=sensor_slot, node_bias=x0_bias)
+               sensor_slot=sensor_slot, node_bias=x0_bias, hops=hops, alpha=alpha)
     wgrad = _WGrad(rowptr, col)
     with _reduce_batch(lib, t.st):
-        dy, dWs, dbs, dbias_ns, wss = _trunk_layer_launches(t, grad_out.contiguous(), xs, ymask, weights, x0bits, wgrad)
-        if L == 0:  # no layer-0 launch applied the node init's relu/dropout mask
+        dy, dWs, dbs, dbias_ns, wss = _trunk_layer_launches(t, grad_out.contiguous(), xs, ymask, weights, x0bits, wgrad,
+                                                            z if hops else None)
+        if hops:
+            dy, dbias_ns = _trunk_diffuse_backward(t, dy, xs[0], nonsensor_idx)
+        elif L == 0:  # no layer-0 launch applied the node init's relu/dropout mask
             dy = dy * (xs[0] > 0) * t.scale
             dbias_ns = dy.index_select(0 if node_major else 1, nonsensor_idx).sum(dim=(0, 1))
         dh_s, dWp, dbp = _sensor_proj_backward(t, dy, h_s, proj_weight, sensor_idx, slot_live, dbias_ns, wss)
@@ -1513,8 +1646,8 @@ def gnn_trunk_backward(grad_out: Tensor, xs: List[Tensor], ymask: Tensor, h_s: T
 
 @gnn_trunk_backward.register_fake
 def _(grad_out, xs, ymask, h_s, proj_weight, weights, sensor_slot, sensor_idx, nonsensor_idx, slot_live, nodetab_t,
-      pairs_t, rowptr_t, col_t, w_t, p, node_major, x0bits, x0_bias, pos_slot_t, rowptr=None, col=None, *, bf16=False,
-      skip=False):
+      pairs_t, rowptr_t, col_t, w_t, p, node_major, x0bits, x0_bias, pos_slot_t, rowptr=None, col=None, z=None, *,
+      bf16=False, skip=False, hops=0, alpha=0.0):
     D = proj_weight.shape[0]
     return (torch.empty_like(h_s), torch.empty_like(proj_weight), grad_out.new_empty(D),
             [torch.empty_like(t) for t in weights], [grad_out.new_empty(D) for _ in weights],
@@ -1522,14 +1655,17 @@ def _(grad_out, xs, ymask, h_s, proj_weight, weights, sensor_slot, sensor_idx, n
 
 
 def _trunk_setup(ctx, inputs, keyword_only_inputs, output):
-    a, f = _trunk_ctx(ctx, gnn_trunk, inputs, output)
+    hops, alpha = int(keyword_only_inputs.get("hops", 0)), float(keyword_only_inputs.get("alpha", 0.0))
+    a, f = _trunk_ctx(ctx, gnn_trunk, inputs, output, hops)
     bf16, skip = bool(keyword_only_inputs.get("bf16", False)), bool(keyword_only_inputs.get("skip", False))
     if ctx.w_grad and bf16:
         raise NotImplementedError("gnn_trunk: the gradient of edge_w exists on the fp32 tier only")
     x0c = f.x0bits.numel() > 0  # x_0 compressed
-    ctx.kw = dict(p=a["p"], node_major=a["node_major"], bf16=bf16, skip=skip)
+    ctx.kw = dict(p=a["p"], node_major=a["node_major"], bf16=bf16, skip=skip,
+                  **(dict(hops=hops, alpha=alpha) if hops else {}))
     # x_0 .. x_L and ymask as returned; the arguments of gnn_trunk_backward by name
-    _save_named(ctx, xs=f.xs, ymask=f.ymask, rowptr=a["rowptr"] if ctx.w_grad else None,
+    _save_named(ctx, xs=f.xs, ymask=f.ymask, **(dict(z=f.z) if hops else {}),
+                rowptr=a["rowptr"] if ctx.w_grad else None,
                 col=a["col"] if ctx.w_grad else None, x0bits=f.x0bits if x0c else None,
                 x0_bias=a["node_bias"] if x0c else None, pos_slot_t=a["pos_slot_t"] if x0c else None,
                 **{k: a[k] for k in ("h_s", "proj_weight", "weights", "sensor_slot", "sensor_idx", "nonsensor_idx",
@@ -1568,13 +1704,15 @@ def gnn_trunk_norm(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights:
                    gammas: List[Tensor], betas: List[Tensor], sensor_slot: Tensor, sensor_idx: Tensor,
                    nonsensor_idx: Tensor, slot_live: Optional[Tensor], nodetab: Tensor, pairs: Tensor, rowptr: Tensor,
                    col: Tensor, nodetab_t: Tensor, pairs_t: Tensor, p: float, eps: float, seed: Tensor,
-                   edge_w: Optional[Tensor] = None) -> List[Tensor]:
+                   edge_w: Optional[Tensor] = None, *, hops: int = 0, alpha: float = 0.0) -> List[Tensor]:
     """[xn_L, x_0 .. x_L, xn_0 .. xn_{L-1}, stats, ymask], all node-major (N, B, D).
     xn_L (the heads' input) is the one differentiable output.  x_l: the residual stream; xn_l: the
     branches' inputs; stats (L + 1, N * B, 2): every norm's (mean, rstd); ymask (L * nmask,) int16:
     layer l's [f_l > 0] words at [l * nmask, (l + 1) * nmask) (gnn_trunk's layout under skip).
     gammas, betas: the L + 1 norms' weight and bias.  The backward keeps x_l AND xn_l per layer,
-    two activations where the skip keeps one.  edge_w: gnn_trunk's autograd anchor."""
+    two activations where the skip keeps one.  edge_w: gnn_trunk's autograd anchor.
+    hops, alpha (keyword-only): gnn_trunk's diffusion stage; the list gains z = z_hops of x_0 as its
+    last entry, the residual stream's start (xn_0 = LN_0(z), x_1 = z + f_0; x_0 stays the node init)."""
     lib = load_library()
     h_s, proj_weight, node_bias = _c(h_s), _c(proj_weight), _c(node_bias)
     weights, biases = [_c(t) for t in weights], [_c(t) for t in biases]
@@ -1591,30 +1729,35 @@ def gnn_trunk_norm(h_s: Tensor, proj_weight: Tensor, node_bias: Tensor, weights:
         raise ValueError(f"gnn_trunk_norm: every norm's weight and bias must be ({D},)")
     if tuple(proj_weight.shape) != (D, Ds + 1):
         raise ValueError(f"proj_weight must be (D, Ds + 1) = ({D}, {Ds + 1}), got {tuple(proj_weight.shape)}")
+    _check_trunk_diffuse("gnn_trunk_norm", hops, alpha)
     N = sensor_slot.shape[0]
-    t = _trunk(lib, h_s, B, N, S, D, L, p, seed, nnz=col.numel(), nodetab=nodetab, pairs=pairs)
+    t = _trunk(lib, h_s, B, N, S, D, L, p, seed, nnz=col.numel(), nodetab=nodetab, pairs=pairs, hops=hops, alpha=alpha)
     dev, st, (dflag, seed_v, sbit) = t.dev, t.st, t.drop
-    out = _alloc(_gnn_trunk_norm_layout(L, B, N, D), h_s)
-    f = trunk_fields("gnn_trunk_norm", out)
+    out = _alloc(_gnn_trunk_norm_layout(L, B, N, D, hops > 0), h_s)
+    f = trunk_fields("gnn_trunk_norm", out, hops > 0)
     xs, xns, stats = f.xs, f.xns, f.stats
     with _timed("node_init", dev):
         check(lib.lg_node_init_proj_fwd(ptr(sensor_slot), ptr(sensor_idx), ptr(h_s), ptr(proj_weight), ptr(node_bias),
                                         ptr(xs[0]), B, N, S, Ds, D, dflag | nat.LG_F_NODE_MAJOR, p, seed_v, 0 | sbit, st),
               "lg_node_init_proj_fwd")
+    if hops:
+        _trunk_diffuse_forward(t, xs[0], f.z)
+    stream = [f.z if hops else xs[0]] + xs[1:]  # the residual stream: it starts at z_K under hops
     with _timed("layernorm_fwd", dev):
-        _ln_fwd(lib, xs[0], None, gammas[0], betas[0], None, xns[0], stats[0], eps, st)
+        _ln_fwd(lib, stream[0], None, gammas[0], betas[0], None, xns[0], stats[0], eps, st)
     for l, (W, b) in enumerate(zip(weights, biases)):
         fl = torch.empty((N, B, D), device=dev, dtype=torch.float32)  # the branch's output, a temporary
         _layer_forward(t, l, xns[l], W, b, fl, _layer_words(f.ymask, l, L), branch=True)
         with _timed("layernorm_fwd", dev):
-            _ln_fwd(lib, xs[l], fl, gammas[l + 1], betas[l + 1], xs[l + 1], xns[l + 1], stats[l + 1], eps, st)
+            _ln_fwd(lib, stream[l], fl, gammas[l + 1], betas[l + 1], xs[l + 1], xns[l + 1], stats[l + 1], eps, st)
     return out
 
 
 @gnn_trunk_norm.register_fake
 def _(h_s, proj_weight, node_bias, weights, biases, gammas, betas, sensor_slot, sensor_idx, nonsensor_idx, slot_live,
-      nodetab, pairs, rowptr, col, nodetab_t, pairs_t, p, eps, seed, edge_w=None):
-    return _alloc(_gnn_trunk_norm_layout(len(weights), h_s.shape[0], sensor_slot.shape[0], proj_weight.shape[0]), h_s)
+      nodetab, pairs, rowptr, col, nodetab_t, pairs_t, p, eps, seed, edge_w=None, *, hops=0, alpha=0.0):
+    return _alloc(_gnn_trunk_norm_layout(len(weights), h_s.shape[0], sensor_slot.shape[0], proj_weight.shape[0],
+                                         hops > 0), h_s)
 
 
 @torch.library.custom_op(f"{NS}::gnn_trunk_norm_backward", mutates_args=(), device_types="cuda")
@@ -1622,7 +1765,8 @@ def gnn_trunk_norm_backward(grad_out: Tensor, xs: List[Tensor], xns: List[Tensor
                             h_s: Tensor, proj_weight: Tensor, weights: List[Tensor], gammas: List[Tensor],
                             sensor_slot: Tensor, sensor_idx: Tensor, nonsensor_idx: Tensor,
                             slot_live: Optional[Tensor], nodetab_t: Tensor, pairs_t: Tensor, p: float,
-                            rowptr: Optional[Tensor] = None, col: Optional[Tensor] = None
+                            rowptr: Optional[Tensor] = None, col: Optional[Tensor] = None, z: Optional[Tensor] = None,
+                            *, hops: int = 0, alpha: float = 0.0
                             ) -> Tuple[Tensor, Tensor, Tensor, List[Tensor], List[Tensor], List[Tensor], List[Tensor],
                                        Tensor]:
     """(dh_s, dproj_weight, dnode_bias, [dW_l], [db_l], [dgamma_l], [dbeta_l], dw).  With s = 1/(1-p)
@@ -1633,11 +1777,18 @@ def gnn_trunk_norm_backward(grad_out: Tensor, xs: List[Tensor], xns: List[Tensor
       a_l   = LNbwd_l(dxn_l) + a_{l+1}                             lg_layernorm_bwd with the carry
     and the entry norm's call applies the node init's mask (LG_F_MASK_OUT: a_0 * s * [x_0 > 0]).
     xs: x_0 .. x_L, xns: xn_0 .. xn_{L-1}.  rowptr, col (the forward CSR): the edge coefficients
-    learn; layer l's share is lg_sddmm_nm on (a_{l+1}, xn_l, the layer's words)."""
+    learn; layer l's share is lg_sddmm_nm on (a_{l+1}, xn_l, the layer's words).
+    z, hops, alpha: the diffusion stage (the entry norm read z = z_hops): its lg_layernorm_bwd runs
+    without the mask and returns dL/dz, then ONE lg_diffuse_bwd runs the adjoint hops and applies the
+    node init's mask from xs[0]."""
     lib = load_library()
     L = len(weights)
     N, B, D = xs[0].shape
-    t = _trunk(lib, grad_out, B, N, h_s.shape[1], D, L, p, nodetab_t=nodetab_t, pairs_t=pairs_t)
+    t = _trunk(lib, grad_out, B, N, h_s.shape[1], D, L, p, nodetab_t=nodetab_t, pairs_t=pairs_t, hops=hops,
+               alpha=alpha)
+    x0 = xs[0]
+    if hops:
+        xs = [z] + list(xs[1:])  # the norms' inputs: the stream starts at z
     dev, st, scale, rows = t.dev, t.st, t.scale, N * B
     wgrad = _WGrad(rowptr, col)
     lnb, gcb = int(lib.lg_layernorm_bwd_workspace_bytes(D)), int(lib.lg_gcn_bwd_nm_workspace_bytes(D))
@@ -1653,7 +1804,8 @@ def gnn_trunk_norm_backward(grad_out: Tensor, xs: List[Tensor], xns: List[Tensor
         w = ws(lnb)
         with _timed("layernorm_bwd", dev):
             check(lib.lg_layernorm_bwd(ptr(dxn), ptr(xs[l]), ptr(stats[l]), ptr(gammas[l]), ptr(carry), ptr(dx), ptr(dg),
-                                       ptr(dbt), rows, D, nat.LG_F_MASK_OUT if l == 0 else 0, scale, ptr(w), w.numel(),
+                                       ptr(dbt), rows, D, nat.LG_F_MASK_OUT if (l == 0 and not hops) else 0, scale,
+                                       ptr(w), w.numel(),
                                        st), "lg_layernorm_bwd")
         dgs[l], dbts[l] = dg, dbt
         return dx
@@ -1667,14 +1819,17 @@ def gnn_trunk_norm_backward(grad_out: Tensor, xs: List[Tensor], xns: List[Tensor
                                                   mask_in=True, mask_out=False, scale_out=1.0, wgrad=wgrad)
             a = ln_bwd(l, dxn, a)
         # a: the node init's pre-activation gradient; its non-sensor rows' sum is the bias's share
-        dbias_ns = a.index_select(0, nonsensor_idx).sum(dim=(0, 1))
+        if hops:
+            a, dbias_ns = _trunk_diffuse_backward(t, a, x0, nonsensor_idx)
+        else:
+            dbias_ns = a.index_select(0, nonsensor_idx).sum(dim=(0, 1))
         dh_s, dWp, dbp = _sensor_proj_backward(t, a, h_s, proj_weight, sensor_idx, slot_live, dbias_ns, wss)
     return dh_s, dWp, dbp, dWs, dbs, dgs, dbts, wgrad.total(dev)
 
 
 @gnn_trunk_norm_backward.register_fake
 def _(grad_out, xs, xns, stats, ymask, h_s, proj_weight, weights, gammas, sensor_slot, sensor_idx, nonsensor_idx,
-      slot_live, nodetab_t, pairs_t, p, rowptr=None, col=None):
+      slot_live, nodetab_t, pairs_t, p, rowptr=None, col=None, z=None, *, hops=0, alpha=0.0):
     D = proj_weight.shape[0]
     return (torch.empty_like(h_s), torch.empty_like(proj_weight), grad_out.new_empty(D),
             [torch.empty_like(t) for t in weights], [grad_out.new_empty(D) for _ in weights],
@@ -1682,11 +1837,12 @@ def _(grad_out, xs, xns, stats, ymask, h_s, proj_weight, weights, gammas, sensor
             grad_out.new_empty(col.shape[0] if col is not None else 0))
 
 
-def _trunk_norm_setup(ctx, inputs, output):
-    a, f = _trunk_ctx(ctx, gnn_trunk_norm, inputs, output)
-    ctx.kw = dict(p=a["p"])
+def _trunk_norm_setup(ctx, inputs, keyword_only_inputs, output):
+    hops, alpha = int(keyword_only_inputs.get("hops", 0)), float(keyword_only_inputs.get("alpha", 0.0))
+    a, f = _trunk_ctx(ctx, gnn_trunk_norm, inputs, output, hops)
+    ctx.kw = dict(p=a["p"], **(dict(hops=hops, alpha=alpha) if hops else {}))
     # the arguments of gnn_trunk_norm_backward by name (xns: xn_0 .. xn_{L-1}, the branches' inputs)
-    _save_named(ctx, xs=f.xs, xns=f.xns[:-1], stats=f.stats, ymask=f.ymask,
+    _save_named(ctx, xs=f.xs, xns=f.xns[:-1], stats=f.stats, ymask=f.ymask, **(dict(z=f.z) if hops else {}),
                 rowptr=a["rowptr"] if ctx.w_grad else None, col=a["col"] if ctx.w_grad else None,
                 **{k: a[k] for k in ("h_s", "proj_weight", "weights", "gammas", "sensor_slot", "sensor_idx",
                                      "nonsensor_idx", "slot_live", "nodetab_t", "pairs_t")})

@@ -487,6 +487,15 @@ def spmm(graph: GCNGraph, x: torch.Tensor, B: int = 1) -> torch.Tensor:
     return y
 
 
+def diffuse(x: torch.Tensor, graph: GCNGraph, hops: int, alpha: float) -> torch.Tensor:
+    """APPNP's propagation of a node-major x (N, B, D), D in {32, 64}: z_0 = x, z_{k+1} = (1 - alpha)
+    Ahat z_k + alpha x, z_hops returned (leakgnn::diffuse: all hops in one LDS-resident launch when
+    the graph fits, else one launch per hop).  Differentiable in x; graph's edge weights are fixed."""
+    from . import library  # noqa: F401  (registers the op)
+    return torch.ops.leakgnn.diffuse(_f32(x), graph.nodetab, graph.pairs, graph.nodetab_t, graph.pairs_t, int(hops),
+                                     float(alpha))
+
+
 # ----------------------------------------------------------------------------- evaluator tails
 # Slot layout of lg_window_metrics' counters (include/leakgnn.h; csrc/metrics.hip holds the same
 # order as an enum and the library refuses a tensor of another length).  The names are those

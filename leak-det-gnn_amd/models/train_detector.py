@@ -174,6 +174,16 @@ def load_predictor(ckpt_path: str | Path, device: torch.device) -> Tuple[nn.Modu
     return model, ckpt
 
 
+def reach_line(detector, args) -> str:
+    """The start-up report of what the trunk can see: a node sees the sensors within gnn_layers +
+    diffuse_hops hops (utils.sensor_reach)."""
+    out_n, out_p = sensor_reach(detector.edge_index_single, len(detector.node_names), detector.sensor_node_idx,
+                                detector.pipe_ends, args.gnn_layers + args.diffuse_hops)
+    return (f"[detector] gnn_layers={args.gnn_layers} skip={args.skip} norm={args.norm} "
+            f"diffuse_hops={args.diffuse_hops}: {out_n}/{len(detector.node_names)} nodes "
+            f"and {out_p}/{detector.pipe_ends.size(0)} pipes (both ends) out of reach of every sensor")
+
+
 def main(argv=None, *, parse_only: bool = False):
     """Train and evaluate.  parse_only: return the parsed namespace (the CLI's flags and their
     defaults) without doing anything else."""
@@ -222,6 +232,11 @@ def main(argv=None, *, parse_only: bool = False):
     ap.add_argument("--norm", type=str, default="none", choices=["none", "layer"],
                     help="layer: pre-norm, a LayerNorm in front of every GCN branch and of the heads "
                          "(needs --skip residual); for trunks of 8 to 12 layers")
+    ap.add_argument("--diffuse_hops", type=int, default=0,
+                    help="propagate the node init this many hops before the first GCN layer (APPNP, no parameters): "
+                         "a node then sees the sensors within gnn_layers + diffuse_hops hops")
+    ap.add_argument("--diffuse_alpha", type=float, default=0.1,
+                    help="teleport weight of the propagation, z = (1 - alpha) Ahat z + alpha x_0, in [0, 1]")
     ap.add_argument("--label_smoothing", type=float, default=0.0,
                     help="label smoothing eps in [0, 1) of the training loss (0: none)")
     ap.add_argument("--smooth_sigma_m", type=float, default=0.0,
@@ -304,10 +319,7 @@ def main(argv=None, *, parse_only: bool = False):
 
     detector = detector_from_args(args.inp_path, sensor_ids, pipe_ids_in_order, vars(args), cls=LeakDetector,
                                   mlp_dtype=args.dtype).to(device)
-    out_n, out_p = sensor_reach(detector.edge_index_single, len(detector.node_names), detector.sensor_node_idx,
-                                detector.pipe_ends, args.gnn_layers)
-    print(f"{now()} [detector] gnn_layers={args.gnn_layers} skip={args.skip} norm={args.norm}: {out_n}/{len(detector.node_names)} nodes "
-          f"and {out_p}/{detector.pipe_ends.size(0)} pipes (both ends) out of reach of every sensor")
+    print(f"{now()} {reach_line(detector, args)}")
     clip = args.grad_clip if args.grad_clip and args.grad_clip > 0 else None
     fused_step = device.type == "cuda"  # clip_grad_norm_ + AdamW.step as one fused op pair
     if fused_step:

@@ -310,7 +310,11 @@ def main():
                     help="time lg_add_layernorm_fwd / lg_layernorm_bwd against the torch composition on the same "
                          "tensors (x + f, F.layer_norm; its backward, then + carry), alternating over --rounds rounds; "
                          "combine with --which '' to time nothing else")
-    ap.add_argument("--rounds", type=int, default=7, help="gru_stack, --skip and --norm legs: rounds of alternating windows")
+    ap.add_argument("--diffuse", action="store_true",
+                    help="time lg_diffuse_fwd / lg_diffuse_bwd at K = 4 and 12: the LDS-resident form (one launch) against "
+                         "the hop-wise form (K launches), each leg one replayed graph, alternating over --rounds rounds; "
+                         "combine with --which '' to time nothing else")
+    ap.add_argument("--rounds", type=int, default=7, help="gru_stack, --skip, --norm and --diffuse legs: rounds of alternating windows")
     ap.add_argument("--window-ms", type=float, default=250.0, help="gru_stack leg: device time per timed window")
     args = ap.parse_args()
     global GRAPH
@@ -480,6 +484,26 @@ def main():
         byts = 4 * rows * D * 4  # four activation-sized passes each way (the torch route moves at least five)
         res["norm"] = {k: {"us_min": min(v), "us_max": max(v), "us": sorted(v)[len(v) // 2],
                            "GBps_4pass": byts / sorted(v)[len(v) // 2] / 1e3} for k, v in runs.items()}
+    if args.diffuse:  # all hops in one LDS-resident launch against one launch per hop, forward and backward (masked)
+        x0 = torch.relu(torch.randn(N, B, D, device=dev))
+        gr, out = torch.randn(N, B, D, device=dev), torch.empty(N, B, D, device=dev)
+        hw = nat.LG_F_DIFFUSE_HOPWISE
+        legs = {}
+        for K in (4, 12):
+            wsf = torch.empty(int(lib.lg_diffuse_workspace_bytes(B, N, D, K, hw, 0)), device=dev, dtype=torch.uint8)
+            wsb = torch.empty(int(lib.lg_diffuse_workspace_bytes(B, N, D, K, hw, 1)), device=dev, dtype=torch.uint8)
+            for tag, fl in (("res", 0), ("hop", hw)):
+                legs[f"fwd_{tag}_K{K}"] = lambda K=K, fl=fl, wsf=wsf: check(lib.lg_diffuse_fwd(
+                    ptr(graph.nodetab), ptr(graph.pairs), ptr(x0), ptr(out), B, N, D, K, 0.1, fl, ptr(wsf), wsf.numel(),
+                    cs()), "diffuse fwd")
+                legs[f"bwd_{tag}_K{K}"] = lambda K=K, fl=fl, wsb=wsb: check(lib.lg_diffuse_bwd(
+                    ptr(graph.nodetab_t), ptr(graph.pairs_t), ptr(gr), ptr(x0), ptr(out), B, N, D, K, 0.1,
+                    fl | nat.LG_F_MASK_OUT, 1.0 / 0.9, ptr(wsb), wsb.numel(), cs()), "diffuse bwd")
+        runs = {k: [] for k in legs}
+        for _ in range(max(1, args.rounds)):
+            for k, f in legs.items():
+                runs[k].append(timeit(f, args.iters))
+        res["diffuse"] = {k: {"us_min": min(v), "us_max": max(v), "us": sorted(v)[len(v) // 2]} for k, v in runs.items()}
     if "node_init" in which:  # sensor projection + node init (x0 = B*N*D fp32 written, node-major)
         S5 = 29
         slot = torch.full((N,), -1, dtype=torch.int32, device=dev)
