@@ -156,6 +156,87 @@ def check_relu_ties(pre64: dict, masks: dict, keep: dict | None = None, rel: flo
     return ties
 
 
+class Arena:
+    """One torch allocation serving ONE entry-point call: its workspaces at exactly the byte counts asked
+    for and every output tensor, each region 256-byte aligned between two guard bands of
+    max(4 KiB, the region's size), at most 1 MiB, so a store up to 2x past a region lands in memory this
+    test owns and compares.  Guards (and the alignment padding) hold GUARD_BYTE; float outputs are
+    pre-filled with NaN, other outputs with 0xFF bytes; poison() fills the workspaces.
+
+      workspaces : {name: nbytes}            outputs : {name: (shape, dtype)}
+      ptr(name)  : the region's device address;  out(name): the output as a tensor view
+      violations(): names of the regions with a changed guard byte (call after torch.cuda.synchronize())"""
+    GUARD_BYTE = 0xFE  # as fp32 / fp64 a huge finite number, as int32 negative: a read of it shows, too
+    ALIGN, MIN_GUARD, MAX_GUARD = 256, 4096, 1 << 20
+    POISONS = ("zeros", "ones", "junk")
+
+    def __init__(self, device, workspaces: dict, outputs: dict):
+        up = lambda n: (n + self.ALIGN - 1) // self.ALIGN * self.ALIGN  # noqa: E731
+        self.spans, self.outs, self.ws = {}, {}, dict(workspaces)
+        sizes = dict(workspaces)
+        for name, (shape, dtype) in outputs.items():
+            assert name not in sizes, name
+            numel = int(np.prod(shape)) if len(shape) else 1
+            sizes[name] = numel * torch.empty((), dtype=dtype).element_size()
+            self.outs[name] = (tuple(shape), dtype)
+        off = 0
+        self.guards = []
+        for name, nbytes in sizes.items():
+            g = up(min(max(self.MIN_GUARD, nbytes), self.MAX_GUARD))
+            self.spans[name] = (off + g, nbytes)
+            self.guards.append((name, off, off + g))                               # before
+            self.guards.append((name, off + g + nbytes, off + g + up(nbytes) + g))  # padding + after
+            off += g + up(nbytes) + g
+        self.buf = torch.full((off + self.ALIGN,), self.GUARD_BYTE, dtype=torch.uint8, device=device)
+        self.base = (-self.buf.data_ptr()) % self.ALIGN  # the allocation is 256-aligned in practice; do not rely on it
+        for name in self.outs:
+            v = self.out(name)
+            if v.dtype.is_floating_point:
+                v.fill_(float("nan"))
+            else:
+                self._bytes(name).fill_(0xFF)
+
+    def _bytes(self, name):
+        a, n = self.spans[name]
+        return self.buf[self.base + a:self.base + a + n]
+
+    def ptr(self, name):
+        a, _ = self.spans[name]
+        p = self.buf.data_ptr() + self.base + a
+        assert p % self.ALIGN == 0
+        return p
+
+    def out(self, name):
+        shape, dtype = self.outs[name]
+        return self._bytes(name).view(dtype).view(shape)
+
+    def poison(self, kind: str, seed: int = 0):
+        """zeros: 0x00; ones: 0xFF (NaN as fp32 and fp64, -1 as int32); junk: random fp32 in +-1e3."""
+        assert kind in self.POISONS, kind
+        for name in self.ws:
+            b = self._bytes(name)
+            if kind == "junk":
+                gen = torch.Generator().manual_seed(seed)
+                n4 = b.numel() // 4
+                junk = (torch.rand(n4, generator=gen) * 2e3 - 1e3).to(b.device)
+                b[:4 * n4].copy_(junk.view(torch.uint8))
+                b[4 * n4:].fill_(0x5A)
+            else:
+                b.fill_(0x00 if kind == "zeros" else 0xFF)
+
+    def violations(self) -> list:
+        bad = []
+        for name, a, b in self.guards:
+            if not bool((self.buf[self.base + a:self.base + b] == self.GUARD_BYTE).all()):
+                g = self.buf[self.base + a:self.base + b]
+                first = int(torch.nonzero(g != self.GUARD_BYTE)[0])
+                start, n = self.spans[name]
+                side = "before" if b <= start else "after"
+                dist = start - (a + first) if side == "before" else a + first - (start + n)
+                bad.append(f"{name}: guard {side} changed, first at {dist} bytes {'in front of' if side == 'before' else 'past'} the region")
+        return bad
+
+
 def oracle_run(sd: dict, r, tf, dt, dev, up=None, lab=None, masks=None, autocast=False, net=None):
     """The oracle detector (oracle/detector_ref.py) in eval mode: (logits, grads, fp64-comparable ReLU
     pre-activations, upstream gradient) for `up`, or for the CE gradient of `lab` in this
